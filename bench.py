@@ -10,14 +10,24 @@ inputs are the model's Init states, so the timed region starts from an empty
 FPSet with nothing precomputed.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload np2|model1|np3_52|fpset] [--deterministic]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warmup
+steps, the K timed steps, the counts checked against the golden fixture,
+one JSON line.  --full adds the measurements that take runs of their own:
+the CPU comparator (cpu_baseline), the other claim mode beside the
+single-GPU line, the sharded loop's per-level fixed cost.  --dump-outputs
+DIR writes what the last timed step returned to its caller as DIR/*.npy
+(float64; dump_outputs below), for comparing two builds output for output.
 
 Claims (round 6): by default the first inserter of a state owns it — TLC
 -workers N semantics, the configuration of the reference's own recorded run
 (KubeAPI___Model_1.launch:33, 4 workers): the same distinct/generated counts,
 depth, level widths and counterexample lengths (checked against the golden
-fixtures on every run).  The single-GPU line also times the deterministic
-mode (every state's first discoverer is TLC -workers 1's: claim stores and
-settle passes) under "deterministic"; --deterministic makes that the line.
+fixtures on every run).  With --full the single-GPU line also times the
+deterministic mode (every state's first discoverer is TLC -workers 1's:
+claim stores and settle passes) under "deterministic"; --deterministic makes
+that the line.
 
 N>1 runs one process per GPU (torch.distributed.run; a plain `python bench.py
 --gpus N` starts that launcher itself as a child process) with the state
@@ -57,9 +67,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="np2", choices=list(WORKLOADS) + ["fpset"])
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baseline, the other claim mode beside the "
+                         "single-GPU line, the sharded loop's per-level fixed cost (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
-                    help="budget of the CPU baseline sample (oracle)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: budget of the CPU baseline sample (oracle)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-timing", action="store_true", help="no per-kernel HIP events")
     ap.add_argument("--all-kernel-timing", action="store_true",
                     help="HIP events on every kernel (default: on the roofline kernel k_claim only;"
@@ -72,7 +87,7 @@ def parse():
     ap.add_argument("--first-claim", action="store_true",
                     help="(the default since round 6; kept for old command lines)")
     ap.add_argument("--no-second-line", "--no-first-claim-line", dest="no_second_line", action="store_true",
-                    help="skip the single-GPU line's measurement of the other claim mode")
+                    help="--full without the single-GPU line's measurement of the other claim mode")
     ap.add_argument("--frontier-hbm-mb", type=int, default=0,
                     help="frontier spill mode: keep the frontiers in a StateQueue with this HBM budget")
     ap.add_argument("--fp-count", type=float, default=1e10,
@@ -87,7 +102,41 @@ def parse():
     ap.add_argument("--launcher-check", action="store_true",
                     help="only start the ranks (gloo, no GPU) and report what each saw: a CPU test of "
                          "the --gpus N self-launch")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy, float64
+    (every count here is below 2^53, so exact).  A BFS check returns counts,
+    not states, so the whole output is a few KB and nothing is sampled.  The
+    inputs are the model's Init states (fpset: the seeded perm63 stream), the
+    same on every run; only the arrays that do not depend on which same-level
+    copy of a state won its claim are written in first-claim mode."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def check_outputs(r: dict, claim_mode) -> dict:
+    """The arrays of one model check's result (CheckResult fields, or the
+    sharded loop's result dict).  act_dist and outdeg_hist split the distinct
+    states by the action / parent that reached them first: in first-claim
+    mode that is run-dependent (TLC -workers N), so they are left out."""
+    def seq(x):
+        return list(x.values()) if isinstance(x, dict) else list(x)
+
+    out = {"counts": [r["init"], r["generated"], r["distinct"], r.get("queue_left", 0), r["depth"], int(r["complete"])],
+           "level_width": seq(r["level_width"]), "act_gen": seq(r["act_gen"])}
+    if claim_mode != "first":
+        out["act_dist"] = seq(r["act_dist"])
+        if r.get("outdeg_hist"):
+            out["outdeg_hist"] = seq(r["outdeg_hist"])
+    return out
 
 
 def launcher_check(args) -> dict:
@@ -449,7 +498,11 @@ def bench_single(args, kw, desc):
             out["kernel_ms_per_step"]["narrow"] = round(narrow[0] / args.steps, 3)
             out["config"]["narrow_levels_per_step"] = narrow[2] // args.steps
     mc.close()
-    if not args.no_second_line and not args.frontier_hbm_mb:
+    if args.dump_outputs:
+        import dataclasses
+
+        dump_outputs(args.dump_outputs, check_outputs(dataclasses.asdict(r), r.claim_mode))
+    if args.full and not args.no_second_line and not args.frontier_hbm_mb:
         # the other claim mode, timed the same way (the headline in
         # first-claim mode only with the deterministic figure beside it)
         out["deterministic" if r.claim_mode == "first" else "first_claim"] = other_mode_line(args, cfg, r)
@@ -527,7 +580,8 @@ def bench_fpset(args):
             raise RuntimeError(f"fpset stress: size {s.size()} found {found} for {n} inserts")
         tin += ti
         tlk += tl
-    load, table_bytes = s.size() / s.capacity(), s.capacity() * 8
+    size, slots = s.size(), s.capacity()
+    load, table_bytes = size / slots, slots * 8
     s.close()
     gbs = n * args.steps * 64 / tin / 1e9
     out = {
@@ -546,7 +600,10 @@ def bench_fpset(args):
                      "kernel": "k_stress_insert", "bytes_per_launch": batch * 64},
     }
     set_traffic(out["roofline"], *pmc_traffic("fpset", "k_stress_insert"))
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        # what the last step left: fingerprints inserted, the set's size, lookups found, slots
+        dump_outputs(args.dump_outputs, {"counts": [n, size, int(found), slots]})
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_fpset(args.fp_load)
     return out
 
@@ -649,6 +706,10 @@ def main():
             out = bench_sharded_fpset(args)
             if out is None:          # not rank 0
                 return
+            if args.dump_outputs:    # inserted, size (checked equal to it every step), found, slots
+                n, c = int(args.fp_count), out["config"]
+                dump_outputs(args.dump_outputs,
+                             {"counts": [n, n, c["lookups_found"], c["table_bytes_per_gpu"] // 8 * out["n_gpus"]]})
         else:
             out = bench_fpset(args)
     else:
@@ -659,9 +720,12 @@ def main():
             out = distributed.bench_sharded(args, kw, desc, golden_check)
             if out is None:          # not rank 0
                 return
+            res = out.pop("_result")
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, check_outputs(res, res.get("claim_mode")))
         else:
             out = bench_single(args, kw, desc)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only (the other ranks returned above), after every rank's
             # timed region; at N > 1 a shorter sample keeps the run within minutes
             secs = args.cpu_seconds if args.gpus == 1 else min(args.cpu_seconds, 10.0)

@@ -8,7 +8,6 @@ import pytest
 from kubecheck import tlc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/KubeAPI.toolbox/Model_1"
 
 
 def test_parse_authored_model1():
@@ -18,14 +17,53 @@ def test_parse_authored_model1():
     assert kw == {"can_fail": False, "can_timeout": False, "invariants": 3}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-def test_parse_reference_toolbox_inputs():
-    # MC.cfg:5-11 binds the constants through MC.tla:5-12 definitions ("<-")
-    defs = tlc.parse_defs(open(os.path.join(REF, "MC.tla")).read())
-    cfg = tlc.parse_cfg(open(os.path.join(REF, "MC.cfg")).read(), defs)
-    assert cfg["specification"] == "Spec"
-    assert cfg["invariants"] == ["TypeOK", "OnlyOneVersion"]
-    assert tlc.model_from_cfg(cfg) == {"can_fail": True, "can_timeout": True, "invariants": 3}
+# Inputs in the layout the TLA+ Toolbox generates for a model (written here,
+# not taken from a toolbox run): the .cfg binds each constant with "<-" to a
+# name that the model's MC module defines, one keyword or value per line,
+# with \* comment lines between the sections.
+TOOLBOX_CFG = """\\* constants of the spec
+CONSTANT defaultInitValue = defaultInitValue
+\\* constants bound through the MC module
+CONSTANT
+REQUESTS_CAN_FAIL <- const_can_fail_1
+\\* the second one
+CONSTANT
+REQUESTS_CAN_TIMEOUT <- const_can_timeout_2
+\\* what to check
+SPECIFICATION
+Spec
+INVARIANT
+TypeOK
+OnlyOneVersion
+\\* end of the generated file
+"""
+TOOLBOX_MODULE = """---- MODULE MC ----
+EXTENDS KubeAPI, TLC
+
+\\* the value of REQUESTS_CAN_FAIL
+const_can_fail_1 ==
+{fail}
+----
+
+\\* the value of REQUESTS_CAN_TIMEOUT
+const_can_timeout_2 ==
+{timeout}
+----
+
+====
+\\* written for tests/test_tlc_cli.py
+"""
+
+
+def test_parse_toolbox_style_inputs():
+    # the .cfg binds the constants through the module's definitions ("<-")
+    for fail, timeout in [(True, True), (True, False), (False, True)]:
+        defs = tlc.parse_defs(TOOLBOX_MODULE.format(fail=str(fail).upper(), timeout=str(timeout).upper()))
+        assert defs == {"const_can_fail_1": str(fail).upper(), "const_can_timeout_2": str(timeout).upper()}
+        cfg = tlc.parse_cfg(TOOLBOX_CFG, defs)
+        assert cfg["specification"] == "Spec"
+        assert cfg["invariants"] == ["TypeOK", "OnlyOneVersion"]
+        assert tlc.model_from_cfg(cfg) == {"can_fail": fail, "can_timeout": timeout, "invariants": 3}
 
 
 def test_rejects_unknown_inputs():

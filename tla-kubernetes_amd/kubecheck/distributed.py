@@ -657,7 +657,7 @@ def bench_sharded(args, kw: dict, desc: str, golden_check=None) -> Optional[dict
     # 3,939 states wide) through the same loop and ranks is nearly all fixed
     # cost (launches, host syncs, collectives)
     fixed = None
-    if native:
+    if native and getattr(args, "full", False):       # (runs of its own: bench.py --full only)
         m1 = NativeShardedChecker(ModelConfig(device=local, keep_trace=False), rank, world)
         try:
             m1.run()
@@ -698,6 +698,8 @@ def bench_sharded(args, kw: dict, desc: str, golden_check=None) -> Optional[dict
                                   "the winning copy of a same-level duplicate is not deterministic)" if first else
                                   "(rank, parent, position) minimum (deterministic)"),
                        "claim_mode": res.get("claim_mode")},
+            # the last timed check's result, for bench.py --dump-outputs (popped before the line is printed)
+            "_result": dict(res, claim_mode=res.get("claim_mode") or ("first" if first else "minimum")),
         }
         if tot_ns > 0:
             achieved = tot_bytes / (tot_ns * 1e-9) / 1e9

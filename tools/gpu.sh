@@ -68,7 +68,7 @@ round|round1)
   cp $O/summary.json $R/profiles/${TAG}_np2_rocprof_summary.json
   cp $O/fpset_summary.json $R/profiles/${TAG}_fpset_rocprof_summary.json
   step bench_np2_pmc
-  timeout -k 10 600 python -u bench.py > $O/bench_np2_pmc.json 2> $O/bench_np2_pmc.err \
+  timeout -k 10 600 python -u bench.py --full > $O/bench_np2_pmc.json 2> $O/bench_np2_pmc.err \
     || { echo BENCH2_FAIL; tail -20 $O/bench_np2_pmc.err; exit 1; }
   cat $O/bench_np2_pmc.json
   [ "$CMD" = round1 ] || bash tools/gpu.sh partb $TAG || exit 1
@@ -82,16 +82,16 @@ parta)
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo SMOKE_FAIL; tail -20 $O/smoke.log; exit 1; }
   cat $O/smoke.log
   step bench_model1
-  timeout -k 10 300 python -u bench.py --workload model1 --steps 5 --warmup 1 --cpu-seconds 5 > $O/bench_model1.json 2> $O/bench_model1.err \
+  timeout -k 10 300 python -u bench.py --full --workload model1 --steps 5 --warmup 1 --cpu-seconds 5 > $O/bench_model1.json 2> $O/bench_model1.err \
     || { echo BENCH1_FAIL; tail -20 $O/bench_model1.err; exit 1; }
   cat $O/bench_model1.json
   step bench_np2
-  timeout -k 10 600 python -u bench.py > $O/bench_np2.json 2> $O/bench_np2.err || { echo BENCH2_FAIL; tail -20 $O/bench_np2.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full > $O/bench_np2.json 2> $O/bench_np2.err || { echo BENCH2_FAIL; tail -20 $O/bench_np2.err; exit 1; }
   cat $O/bench_np2.json
   pmc "" $O/summary.json python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-timing --no-first-claim-line || exit 1
   # FPSet stress (BASELINE config 4): the bench line at 1e10 fps, PMC passes at 2^30
   step bench_fpset
-  timeout -k 10 300 python -u bench.py --workload fpset --steps 2 --warmup 1 > $O/bench_fpset.json 2> $O/bench_fpset.err \
+  timeout -k 10 300 python -u bench.py --full --workload fpset --steps 2 --warmup 1 > $O/bench_fpset.json 2> $O/bench_fpset.err \
     || { echo BENCHF_FAIL; tail -20 $O/bench_fpset.err; exit 1; }
   cat $O/bench_fpset.json
   pmc f $O/fpset_summary.json python3 $R/bench.py --workload fpset --fp-count 1073741824 --steps 1 --warmup 0 || exit 1
@@ -102,7 +102,7 @@ partb)
   # (the box's copy of profiles/: the bench line below finds this build's PMC)
   cp $O/np3_summary.json $R/profiles/${TAG}_np3_52_rocprof_summary.json
   step bench_np3
-  timeout -k 10 400 python -u bench.py --workload np3_52 --steps 3 --warmup 1 --cpu-seconds 10 > $O/bench_np3.json 2> $O/bench_np3.err \
+  timeout -k 10 400 python -u bench.py --full --workload np3_52 --steps 3 --warmup 1 --cpu-seconds 10 > $O/bench_np3.json 2> $O/bench_np3.err \
     || { echo NP3_BENCH_FAIL; tail -20 $O/bench_np3.err; exit 1; }
   cat $O/bench_np3.json
   step sharded_pmc
@@ -110,7 +110,7 @@ partb)
   PMC_EXTRA="--algorithmic $O/sh_alg.json" pmc sh $O/np2_sharded_summary.json python3 $R/tools/sharded_profile.py 8 || exit 1
   cp $O/np2_sharded_summary.json $R/profiles/${TAG}_np2_sharded_rocprof_summary.json
   step bench_sharded
-  timeout -k 10 400 python -u bench.py --sharded --steps 3 --warmup 1 --cpu-seconds 10 > $O/bench_np2_sharded_world1.json 2> $O/bench_sharded.err \
+  timeout -k 10 400 python -u bench.py --full --sharded --steps 3 --warmup 1 --cpu-seconds 10 > $O/bench_np2_sharded_world1.json 2> $O/bench_sharded.err \
     || { echo SHBENCH_FAIL; tail -20 $O/bench_sharded.err; exit 1; }
   cat $O/bench_np2_sharded_world1.json
   bash tools/gpu.sh levels $TAG || exit 1

@@ -24,7 +24,7 @@ first)
     || { echo TESTS_FAIL; grep -E "FAIL|Error|assert" $O/tests.log | head -30; tail -30 $O/tests.log; exit 1; }
   tail -3 $O/tests.log
   step bench
-  timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_np2.json 2> $O/bench_np2.err \
+  timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_np2.json 2> $O/bench_np2.err \
     || { echo BENCH_FAIL; tail $O/bench_np2.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_np2.json'));print(d['ms_per_step'], d['kernel_ms_per_step'], d['roofline']['frac'], d.get('first_claim'))"
   for M in "" "--first"; do
@@ -74,7 +74,7 @@ graph)
     done
   done
   step bench_np2
-  timeout -k 10 300 python -u bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_np2.json 2> $O/bench_np2.err \
+  timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_np2.json 2> $O/bench_np2.err \
     || { echo BENCH_FAIL; tail -20 $O/bench_np2.err; exit 1; }
   cat $O/bench_np2.json
   ;;
