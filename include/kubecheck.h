@@ -461,6 +461,28 @@ int kc_exchange_plan(int world, int me, const uint64_t *Mx, uint64_t piece_recor
  * answers (0 expected).  No GPU needed. */
 int64_t kc_cold_find_selftest(uint64_t n, uint64_t seed);
 
+/* ------------------------------------------------- Probe primitives (tests) */
+/* Device harness for the seen-set probe loops (csrc/probe_selftest.hip): runs
+ * n operations of one kind through the product's device functions on a table
+ * of exactly nslots slots (any size >= 2; even for the compact table, whole
+ * 8-slot buckets for the FPSet, a power of two at most half full for the batch
+ * table, the LDS table's own size for the LDS kinds), zeroed or pre-loaded
+ * from table_in, and copies back one result word per operation and the final
+ * table image (u64 words: 1 per slot for the FPSet and the compact table,
+ * {fp, ~claim} / {fp, key} for the others).  mode 0: one lane runs the
+ * operations in order; 1: one lane per operation in one launch.  Kinds:
+ * 0 fpset_insert, 1 fpset_contains, 2 claimset_claim, 3 the STORE-claim
+ * protocol (three launches; res_out[n + i] = operation i holds the slot's
+ * claim), 4 claimset_get, 5 claimset_insert_from, 6 fpslots_insert_pair,
+ * 7 the same in k_claim's pipelined order, 8 the same from a given pair
+ * (keys[2i], keys[2i + 1]), 9 batch_insert + batch_is_rep, 10 / 11 lds_claim
+ * of the engine / the sharded tile, 12-14 the ClaimSet / compact / FPSet
+ * rehash kernel (table_in: the old table of n slots; res_out[0] = failures).
+ * keys: the claim keys (claim = level << 44 | key).  Test-only. */
+int kc_probe_selftest(int kind, uint64_t nslots, const uint64_t *fps, const uint64_t *keys, uint64_t n,
+                      uint32_t level, int mode, const uint64_t *table_in, uint64_t *res_out,
+                      uint64_t *table_out);
+
 /* ---------------------------------------------------------- Spec (host) */
 /* Words of the canonical tuple for a model: 1 + 19 * (nc + np + ns). */
 int kc_spec_tuple_words(int nc, int np, int ns);

@@ -465,7 +465,7 @@ FIRST_CASES = TLC_CASES + (("variant5", dict(variant=5), "invariant"),)
 
 
 def _first_trace_ok(oracle, kw, trace):
-    cfg = oracle.config(nc=kw.get("nc", 1), ns=kw.get("ns", 1), variant=kw.get("variant", 0),
+    cfg = oracle.config(nc=kw.get("nc", 1), np_=kw.get("np", 1), ns=kw.get("ns", 1), variant=kw.get("variant", 0),
                         invariants=kw.get("invariants", 3))
     init = {tuple(map(int, t)) for t in oracle.level_tuples(cfg, 1)}
     assert tuple(trace[0]) in init
@@ -513,7 +513,7 @@ def test_native_owner_chunk_scan_off(fixtures, monkeypatch, first):
     assert r["level_width"] == fx["level_width"] and r["act_gen"] == fx["act_gen"]
 
 
-def test_native_first_claim_np2(fixtures):
+def test_native_first_claim_np2(fixtures, oracle):
     # NP=2: the 40-level prefix at 4 emulated ranks, and the seeded race's
     # NoLostUpdate violation at depth 25 (wide, deferred levels) at 3
     fx = fixtures["np2_40levels"]
@@ -524,6 +524,9 @@ def test_native_first_claim_np2(fixtures):
     r = native(3, np=2, variant=1, invariants=7, first_claim=True)
     assert r["error"] == "invariant" and r["error_invariant"] == "NoLostUpdate"
     assert (r["error_level"], r["trace_len"]) == (fk["err_level"], fk["trace_len"])
+    assert r["claim_mode"] == "first"
+    # the trace is a behaviour of the NP=2 variant-1 model from an Init state
+    _first_trace_ok(oracle, dict(np=2, variant=1, invariants=7), r["trace"])
 
 
 def test_native_enlarged_full_emulated_first_claim(fixtures):

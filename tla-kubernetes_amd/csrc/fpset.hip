@@ -84,7 +84,7 @@ int DevFpset::reserve(uint64_t extra, hipStream_t st) {
   KC_HIP_TRY(hipMemsetAsync(ns, 0, nb * 64, st));
   KC_HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), st));
   const uint64_t old_slots = capacity();
-  hipLaunchKernelGGL(k_fpset_rehash, dim3(table_grid(old_slots)), dim3(256), 0, st, slots, old_slots, ns, nb, d_fail);
+  launch_fpset_rehash(slots, old_slots, ns, nb, d_fail, st);
   KC_HIP_TRY(hipGetLastError());
   unsigned long long fail = 0;
   KC_HIP_TRY(hipMemcpyAsync(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost, st));
@@ -169,6 +169,22 @@ __global__ void k_fpslots_insert_list(const uint64_t* __restrict__ fps, uint64_t
   }
 }
 
+void launch_fpset_rehash(const unsigned long long* old, uint64_t old_slots, unsigned long long* nw,
+                         uint64_t new_buckets, unsigned long long* d_fail, hipStream_t st) {
+  hipLaunchKernelGGL(k_fpset_rehash, dim3(table_grid(old_slots)), dim3(256), 0, st, old, old_slots, nw, new_buckets,
+                     d_fail);
+}
+void launch_claimset_rehash(const ClaimEntry* old, uint64_t old_slots, ClaimEntry* nw, uint64_t new_slots,
+                            unsigned long long* d_fail, hipStream_t st) {
+  hipLaunchKernelGGL(k_claimset_rehash, dim3(table_grid(old_slots)), dim3(256), 0, st, old, old_slots, nw, new_slots,
+                     d_fail);
+}
+void launch_fpslots_rehash(const unsigned long long* old, uint64_t old_slots, unsigned long long* nw,
+                           uint64_t new_slots, unsigned long long* d_fail, hipStream_t st) {
+  hipLaunchKernelGGL(k_fpslots_rehash, dim3(table_grid(old_slots)), dim3(256), 0, st, old, old_slots, nw, new_slots,
+                     d_fail);
+}
+
 void launch_claimset_insert_list(const uint64_t* d_fps, uint64_t n, const DevClaimSet& cs,
                                  uint32_t level, int* d_res, hipStream_t st) {
   if (n && cs.compact)
@@ -239,11 +255,9 @@ int DevClaimSet::reserve(uint64_t extra, hipStream_t st) {
   KC_HIP_TRY(hipMemsetAsync(nt, 0, ns * slot_bytes(), st));
   KC_HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), st));
   if (compact)
-    hipLaunchKernelGGL(k_fpslots_rehash, dim3(table_grid(nslots)), dim3(256), 0, st,
-                       words(), nslots, reinterpret_cast<unsigned long long*>(nt), ns, d_fail);
+    launch_fpslots_rehash(words(), nslots, reinterpret_cast<unsigned long long*>(nt), ns, d_fail, st);
   else
-    hipLaunchKernelGGL(k_claimset_rehash, dim3(table_grid(nslots)), dim3(256), 0, st,
-                       t, nslots, nt, ns, d_fail);
+    launch_claimset_rehash(t, nslots, nt, ns, d_fail, st);
   KC_HIP_TRY(hipGetLastError());
   unsigned long long fail = 0;
   KC_HIP_TRY(hipMemcpyAsync(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost, st));

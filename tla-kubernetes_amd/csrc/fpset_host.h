@@ -62,6 +62,15 @@ struct DevBatchTable {
   void release();
 };
 
+// the rehash passes of reserve(): every entry of `old` into the zeroed `nw`;
+// *d_fail counts the entries that found no slot
+void launch_fpset_rehash(const unsigned long long* old, uint64_t old_slots, unsigned long long* nw,
+                         uint64_t new_buckets, unsigned long long* d_fail, hipStream_t st);
+void launch_claimset_rehash(const ClaimEntry* old, uint64_t old_slots, ClaimEntry* nw, uint64_t new_slots,
+                            unsigned long long* d_fail, hipStream_t st);
+void launch_fpslots_rehash(const unsigned long long* old, uint64_t old_slots, unsigned long long* nw,
+                           uint64_t new_slots, unsigned long long* d_fail, hipStream_t st);
+
 uint64_t next_pow2(uint64_t x);
 // insert a device list of (normalised) fps; d_res[i] = 1 new / 0 present (may be NULL)
 void launch_fpset_insert_list(const uint64_t* d_fps, uint64_t n, const DevFpset& fs, int* d_res,

@@ -317,7 +317,7 @@ class NativeShardedChecker:
         r = KcResult()
         check("kc_shard_result", self._lib.kc_shard_result(self._shards[i], C.byref(r)))
         return {"generated": int(r.generated), "init": int(r.init), "distinct": int(r.distinct),
-                "deferred": int(r.deferred_states)}
+                "deferred": int(r.deferred_states), "fpset_slots": int(r.fpset_slots)}
 
     def close(self) -> None:
         if self._g:
