@@ -460,6 +460,63 @@ int kc_exchange_plan(int world, int me, const uint64_t *Mx, uint64_t piece_recor
  * whole-run and through staging windows.  Returns the number of wrong
  * answers (0 expected).  No GPU needed. */
 int64_t kc_cold_find_selftest(uint64_t n, uint64_t seed);
+/* The same host search on the caller's n strictly ascending keys and m
+ * queries (each 1 to 2^21): views[i] = the number of views of the run in
+ * which q[i] is found, the views being the whole run (window 0) or its
+ * staging windows of `window` keys (a multiple of 8): 1 for a present key, 0
+ * for an absent one.  No GPU needed. */
+int kc_cold_find_keys_selftest(const uint64_t *keys, uint64_t n, const uint64_t *q, uint64_t m, uint64_t window,
+                               uint8_t *views);
+/* cold_key (unkey 0) or cold_unkey (1) of n words, on the host (on_device 0)
+ * or in a kernel (1). */
+int kc_cold_key_selftest(const uint64_t *in, uint64_t *out, uint64_t n, int unkey, int on_device);
+
+/* ------------------------------------------------ Cold tier driven directly (tests) */
+/* A kc::ColdSet (csrc/coldset.h) of its own, on a stream of its own
+ * (csrc/coldset_selftest.hip).  The arguments are ColdSet::Config's:
+ * meta_hbm_bytes / host_bytes 0 = unlimited, dir NULL or "" = no spill
+ * directory, window_keys a multiple of 8 in [64, 2^23].  The harness keeps the
+ * kernels inside their buffers: -EINVAL, before any launch, for keys not
+ * strictly ascending, queries not ascending, n or m of 0 or above 2^21; and
+ * after a failed add (which leaves a run without a directory in the set)
+ * probe, all_keys and add_run answer -EINVAL until clear. */
+int kc_coldset_create(uint64_t meta_hbm_bytes, uint64_t host_bytes, const char *dir, uint64_t window_keys,
+                      int bloom_bits, int cache_keys, int merge_div, int merge_threads, void **out);
+/* Uploads the n host keys and adds them as a run (ColdSet::add_run). */
+int kc_coldset_add_run(void *h, const uint64_t *keys, uint64_t n);
+/* Uploads the m queries, the caller's found bytes and hit counter, probes
+ * (ColdSet::probe), synchronises and copies both back. */
+int kc_coldset_probe(void *h, const uint64_t *q, uint64_t m, uint8_t *found, uint64_t *hits);
+/* The integer fields of ColdStats, in this order: runs, runs_disk, keys,
+ * host_bytes, disk_bytes, meta_bytes, peak_meta_bytes, merges, merged_keys,
+ * disk_written, disk_read, windows_skipped, cached_runs, cached_keys,
+ * cache_bytes, cache_uploaded, filter_tests, filter_passed, merge_probes. */
+#define KC_COLDSET_NSTATS 19
+int kc_coldset_stats(void *h, uint64_t *out);
+/* ColdSet::all_keys: the first `cap` of the merged keys into out; returns how
+ * many there are (reading a file run counts in disk_read). */
+int64_t kc_coldset_all_keys(void *h, uint64_t *out, uint64_t cap);
+int kc_coldset_clear(void *h);
+void kc_coldset_destroy(void *h);
+
+/* --------------------------------- Kernels joining the seen-set's tiers (tests) */
+/* One launch of a kernel of csrc/engine_spill.h, as the engine launches it
+ * (csrc/spill_selftest.hip), for Model<1,np,1>, np 1 or 2, with the default
+ * constants.  Every index a kernel derives from its input is checked on the
+ * host first (-EINVAL).  By kind:
+ * 0 k_claimset_keys: a = table image ({fp, ~claim} per slot), na = slots;
+ *   out = nout >= cap words, uploaded as given and copied back; res[0] = count.
+ * 1 k_spill_queries: a = na packed parents; b[i] = newmask of parent i (nb =
+ *   na; bits below its successor count only); c = nc exclusive winner sums per
+ *   256-parent tile; out = qkey and res = qloc, nout words each, uploaded as
+ *   given and copied back.
+ * 2 k_spill_apply: a = table image, na = slots; b = nb x {qkey, qloc, found};
+ *   c = newmask of the nc = cap parents (a found query's bit is set, once);
+ *   tile_total starts at each tile's popcount.  out = table image (nout = 2 na);
+ *   res = [Counters::overflow, newmask x nc, tile_total per 256 parents].
+ * 3 k_tile_succ: a = na packed parents; res[t] = successors of tile t. */
+int kc_spill_selftest(int kind, int np, const uint64_t *a, uint64_t na, const uint64_t *b, uint64_t nb,
+                      const uint64_t *c, uint64_t nc, uint64_t cap, uint64_t *out, uint64_t nout, uint64_t *res);
 
 /* ------------------------------------------------- Probe primitives (tests) */
 /* Device harness for the seen-set probe loops (csrc/probe_selftest.hip): runs

@@ -14,8 +14,9 @@
 //   * optionally a blocked Bloom filter (one 64-B block per key, 6 bits), so
 //     most lookups of truly new states never leave HBM.
 // Runs are size-tiered: a new run is merged (on the host, by key range in
-// parallel threads) with the previous one while that one is at most twice
-// its size, so a query probes O(log flushes) runs.
+// parallel threads) with the previous one while that one is at most 1.5
+// times its size (or the set holds more than 12 runs), so a query probes
+// O(log flushes) runs.
 //
 // Keys are cold_key(fp): a bijective 64-bit mix of the fingerprint, uniform
 // in every bit (a fingerprint's top bits are the owner bits, a projection

@@ -356,6 +356,7 @@ void ColdSet::clear() {
   runs_.clear();
   if (d_stat_) (void)hipMemset(d_stat_, 0, 16);
   merges_ = merged_keys_ = disk_written_ = disk_read_ = windows_skipped_ = 0;
+  merge_probes_ = 0;
   cache_uploaded_ = 0;
   t_pin_ = t_merge_ = t_meta_ = t_evict_ = 0;
   peak_meta_ = meta_used_;
@@ -690,6 +691,21 @@ int ColdSet::all_keys(std::vector<uint64_t>& out) {
 
 }  // namespace kc
 
+// the directory of sorted keys as build_meta sizes it and k_run_meta fills it
+static std::vector<uint64_t> host_dir(const std::vector<uint64_t>& keys, int* dbits_out) {
+  using namespace kc;
+  const uint64_t n = keys.size();
+  int dbits = 1;
+  while ((1ull << (dbits + 1)) * 16 <= n && dbits < 40) ++dbits;
+  std::vector<uint64_t> dir((1ull << dbits) + 1);
+  for (uint64_t b = 0, i = 0; b <= (1ull << dbits); ++b) {
+    while (i < n && dir_bucket(keys[i], dbits) < b) ++i;
+    dir[b] = i;
+  }
+  *dbits_out = dbits;
+  return dir;
+}
+
 // Host self-check of the cold-run search (no GPU): n sorted random keys with
 // the directory the kernels build, every key found, absent keys (including
 // ones between two lines' ranges) not found, each through whole-run and
@@ -705,13 +721,8 @@ extern "C" int64_t kc_cold_find_selftest(uint64_t n, uint64_t seed) {
   std::sort(keys.begin(), keys.end());
   keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
   n = keys.size();
-  int dbits = 1;
-  while ((1ull << (dbits + 1)) * 16 <= n && dbits < 40) ++dbits;
-  std::vector<uint64_t> dir((1ull << dbits) + 1);
-  for (uint64_t b = 0, i = 0; b <= (1ull << dbits); ++b) {
-    while (i < n && dir_bucket(keys[i], dbits) < b) ++i;
-    dir[b] = i;
-  }
+  int dbits;
+  const std::vector<uint64_t> dir = host_dir(keys, &dbits);
   int64_t bad = 0;
   const uint64_t W = 64 + (n / 7 & ~7ull);      // windows of W keys (a multiple of 8)
   auto find_any = [&](uint64_t k) {
@@ -737,4 +748,31 @@ extern "C" int64_t kc_cold_find_selftest(uint64_t n, uint64_t seed) {
   bad += find_any(0) != (n && keys[0] == 0);
   bad += find_any(~0ull) != (n && keys[n - 1] == ~0ull);
   return bad;
+}
+
+// The same host search on the caller's keys (strictly ascending) and queries:
+// views[i] = the number of views of the run in which q[i] is found, the views
+// being the whole run (window == 0) or its staging windows of `window` keys
+// (a multiple of 8).  1 for a present key, 0 for an absent one.
+extern "C" int kc_cold_find_keys_selftest(const uint64_t* keys_in, uint64_t n, const uint64_t* q, uint64_t m,
+                                          uint64_t window, uint8_t* views) {
+  using namespace kc;
+  bool ok = keys_in && q && views && n >= 1 && n <= (1ull << 21) && m >= 1 && m <= (1ull << 21) && (window & 7) == 0;
+  for (uint64_t i = 1; ok && i < n; ++i) ok = keys_in[i - 1] < keys_in[i];
+  if (!ok) {
+    set_error("kc_cold_find_keys_selftest: bad argument (1 to 2^21 strictly ascending keys and queries, window a "
+              "multiple of 8)");
+    return -EINVAL;
+  }
+  const std::vector<uint64_t> keys(keys_in, keys_in + n);
+  int dbits;
+  const std::vector<uint64_t> dir = host_dir(keys, &dbits);
+  const uint64_t W = window ? window : n;
+  for (uint64_t i = 0; i < m; ++i) {
+    int c = 0;
+    for (uint64_t w0 = 0; w0 < n; w0 += W)
+      c += run_find(q[i], keys.data() + w0, w0, std::min(n, w0 + W), dir.data(), dbits) ? 1 : 0;
+    views[i] = (uint8_t)c;
+  }
+  return 0;
 }

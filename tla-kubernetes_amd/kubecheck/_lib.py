@@ -171,6 +171,18 @@ SIGNATURES = [
     ("kc_group_records_sent", C.c_uint64, [_P]),
     ("kc_exchange_plan", C.c_int, [C.c_int, C.c_int, _U64P, C.c_uint64, _U64P, C.c_int]),
     ("kc_cold_find_selftest", C.c_int64, [C.c_uint64, C.c_uint64]),
+    ("kc_cold_find_keys_selftest", C.c_int, [_U64P, C.c_uint64, _U64P, C.c_uint64, C.c_uint64, _U8P]),
+    ("kc_cold_key_selftest", C.c_int, [_U64P, _U64P, C.c_uint64, C.c_int, C.c_int]),
+    ("kc_coldset_create", C.c_int, [C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.POINTER(_P)]),
+    ("kc_coldset_add_run", C.c_int, [_P, _U64P, C.c_uint64]),
+    ("kc_coldset_probe", C.c_int, [_P, _U64P, C.c_uint64, _U8P, _U64P]),
+    ("kc_coldset_stats", C.c_int, [_P, _U64P]),
+    ("kc_coldset_all_keys", C.c_int64, [_P, _U64P, C.c_uint64]),
+    ("kc_coldset_clear", C.c_int, [_P]),
+    ("kc_coldset_destroy", None, [_P]),
+    ("kc_spill_selftest", C.c_int, [C.c_int, C.c_int, _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64,
+                                    C.c_uint64, _U64P, C.c_uint64, _U64P]),
     ("kc_probe_selftest", C.c_int, [C.c_int, C.c_uint64, _U64P, _U64P, C.c_uint64, C.c_uint32, C.c_int, _U64P,
                            _U64P, _U64P]),
     ("kc_spec_tuple_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
