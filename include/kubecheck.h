@@ -34,6 +34,9 @@
  *   kc_engine_*  tlc2.TLC's BFS ModelChecker run over Model_1-style inputs
  *                (MC.cfg:1-16, MC.tla:1-16, KubeAPI___Model_1.launch):
  *                counts, depth, per-action coverage and counterexamples.
+ *   kc_sim_*     tlc2.TLC -simulate: bounded random behaviours checked
+ *                against the same invariants, Asserts and deadlock (the
+ *                reference holds no simulation run; semantics below).
  *   kc_spec_*    host-side access to the lowered spec (canonical tuples) —
  *                used for trace replay and by the parity tests.
  */
@@ -452,6 +455,98 @@ uint64_t kc_group_records_sent(const kc_group *g);
  * how many there are.  Host only (no GPU): the CPU tests check every rank's
  * plan pairs with its peers' for world 1..9. */
 int kc_exchange_plan(int world, int me, const uint64_t *Mx, uint64_t piece_records, uint64_t *out, int cap);
+
+/* ---------------------------------------------------------- Simulation */
+/* Simulation mode (TLC's -simulate): num_walks bounded random behaviours on
+ * one GPU, one lane per walk, each state checked against the invariants, the
+ * Asserts and deadlock.  For models whose state space no BFS can finish.
+ *
+ * RNG (counter-based; csrc/simulate.h, the same code on device and host):
+ *   mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x>>30) * 0xBF58476D1CE4E5B9;
+ *           x = (x ^ x>>27) * 0x94D049BB133111EB; return x ^ x>>31  (mod 2^64)
+ *   K(w)    = mix(mix(seed) ^ w)
+ *   r(w, k) = mix(K(w) ^ k)
+ *   pick(r, n) = floor(r * n / 2^64)
+ *
+ * Walk w, 0 <= w < num_walks, has states s_0, s_1, ...; s_0 is Init state
+ * pick(r(w, 0), num_init) in kc_spec_init order.  At s_k (k + 1 states so
+ * far), in this order:
+ *   1. the invariants of cfg.invariants in MC.cfg order: a violation ends the
+ *      walk with kind invariant, trace_len = k + 1 (an Init state included,
+ *      as in the BFS);
+ *   2. if k + 1 == depth the walk ends at the depth limit, not expanded
+ *      (depth = the most states in a behaviour, TLC's -depth);
+ *   3. an Assert raised while evaluating Next ends it with kind assertion
+ *      (whichever successor would have been chosen), trace_len = k + 1;
+ *   4. no successor: kind deadlock with cfg.check_deadlock, else the walk has
+ *      terminated (no error);
+ *   5. else s_{k+1} = successor pick(r(w, k + 1), total) in
+ *      kc_spec_successors order; one step is counted for its action.
+ * The result is a function of (model, seed, num_walks, depth) alone, whatever
+ * steps_per_launch.  The error reported is the error walk with the smallest
+ * (trace_len, walk).  The device keeps no trace: kc_sim_replay recomputes a
+ * walk on the host, and kc_sim_trace checks that replay against the kind,
+ * length and final state the device recorded.
+ * stop_on_error = 1: no launch is made after the first one in which a walk
+ * erred; the walks advance in lock-step, so the error reported is the same and
+ * the totals cover the steps run.
+ * count_distinct = 1: distinct_visited = distinct states visited over all
+ * walks (Init states included), by 63-bit fingerprint in an HBM FPSet that is
+ * grown before each launch to hold live walks x steps more (-ENOMEM if it
+ * cannot be). */
+#define KC_SIM_MAX_DEPTH 65535
+#define KC_SIM_MAX_WALKS (1ull << 30)
+/* kc_sim_walks / kc_sim_replay kinds: kc_result.err_kind's 1-3, then */
+#define KC_SIM_RUNNING 0      /* stopped early by stop_on_error */
+#define KC_SIM_DEPTH 4        /* ended at the depth limit */
+#define KC_SIM_TERMINATED 5   /* no successor, check_deadlock off */
+typedef struct {
+  uint64_t seed;
+  uint64_t num_walks;        /* 1 .. 2^30 */
+  int depth;                 /* 1 .. KC_SIM_MAX_DEPTH */
+  int steps_per_launch;      /* 0 = default */
+  int count_distinct;
+  int stop_on_error;
+} kc_sim_config;
+typedef struct {
+  uint64_t steps;                     /* successor choices made */
+  uint64_t act_steps[KC_NACTIONS];    /* ... per action */
+  uint64_t walks_error, walks_depth, walks_terminated;
+  uint64_t distinct_visited;          /* with count_distinct */
+  int err_kind;                       /* as in kc_result; 0 none */
+  int err_action, err_self, err_invariant;
+  int trace_len;                      /* states of the reported error walk */
+  uint64_t err_walk;
+  double seconds;                     /* host wall time of the run */
+  double kernel_ms;                   /* HIP events around the walk launches */
+  uint64_t launches;                  /* walk launches */
+  uint64_t fpset_slots;               /* visited-state table at the end (count_distinct) */
+} kc_sim_result;
+typedef struct kc_sim kc_sim;
+/* Model validation and errors as kc_engine_create (-EINVAL, -ENODEV without a
+ * GPU, -ENOMEM); the BFS-only fields of the model config are ignored. */
+int kc_sim_create(const kc_model_config *cfg, const kc_sim_config *sim, kc_sim **out);
+void kc_sim_destroy(kc_sim *s);
+int kc_sim_run(kc_sim *s, kc_sim_result *res);
+/* Every walk of the last run: how it ended, its number of states and its final
+ * state as a canonical tuple (final_tuples_out may be NULL). */
+int kc_sim_walks(kc_sim *s, uint32_t *kind_out, uint32_t *len_out, uint64_t *final_tuples_out);
+/* The behaviour of `walk`, replayed on the host and checked against the
+ * device's record (-EIO on a mismatch): up to `cap` states as canonical tuples
+ * and the action that led to each (-1 for the Init state); returns the number
+ * of states. */
+int kc_sim_trace(kc_sim *s, uint64_t walk, uint64_t *tuples_out, int *actions_out, int cap);
+/* The same as TLC-style text ("State 1: ..."); returns bytes needed or < 0. */
+int64_t kc_sim_trace_text(kc_sim *s, uint64_t walk, char *buf, size_t cap);
+/* Host copies of the RNG: r(walk, k) and pick(r, n). */
+uint64_t kc_sim_rand(uint64_t seed, uint64_t walk, uint64_t k);
+uint64_t kc_sim_pick(uint64_t r, uint64_t n);
+/* One walk on the host (no GPU needed, no state kept): the steps above run
+ * through the host build of the spec code the kernel uses.  Writes up to `cap`
+ * states and actions (either may be NULL), *kind_out = how the walk ended;
+ * returns the number of states. */
+int kc_sim_replay(const kc_model_config *cfg, uint64_t seed, int depth, uint64_t walk,
+                  uint64_t *tuples_out, int *actions_out, int cap, int *kind_out);
 
 /* ----------------------------------------------- Seen-set spill (tests) */
 /* Host self-check of the cold tier's run search (coldset.hip run_find, the

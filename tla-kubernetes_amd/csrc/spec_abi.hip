@@ -15,6 +15,7 @@
 #include "kc_common.h"
 #include "kubeapi_spec.h"
 #include "record.h"
+#include "simulate.h"
 
 namespace kc {
 
@@ -298,6 +299,44 @@ int kc_spec_pack(const kc_model_config* cfg, const uint64_t* tuple, uint64_t* pa
     if (!M::from_tuple(tuple, s)) { set_error("kc_spec_pack: bad tuple"); return -EINVAL; }
     for (int i = 0; i < M::W; ++i) packed[i] = s.w[i];
     return M::W;
+  });
+}
+
+// ---- simulation mode: the RNG and one walk on the host (simulate.h; the
+// walk kernel of simulate.hip runs the same sim_step)
+uint64_t kc_sim_rand(uint64_t seed, uint64_t walk, uint64_t k) {
+  return sim_rand_key(sim_key(sim_mix(seed), walk), k);
+}
+uint64_t kc_sim_pick(uint64_t r, uint64_t n) { return sim_pick(r, n); }
+
+int kc_sim_replay(const kc_model_config* cfg, uint64_t seed, int depth, uint64_t walk, uint64_t* tuples,
+                  int* actions, int cap, int* kind_out) {
+  if (!cfg) { set_error("kc_sim_replay: NULL"); return -EINVAL; }
+  if (depth < 1 || depth > KC_SIM_MAX_DEPTH) {
+    set_error("kc_sim_replay: depth %d outside 1..%d", depth, KC_SIM_MAX_DEPTH);
+    return -EINVAL;
+  }
+  return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {
+    using M = decltype(m);
+    const Flags f = flags_of(*cfg);
+    const uint64_t key = sim_key(sim_mix(seed), walk);
+    typename M::State s;
+    M::init_state((int)sim_pick(sim_rand_key(key, 0), (uint64_t)M::num_init()), s, cfg->variant);
+    int action = -1;
+    for (uint32_t k = 0;; ++k) {           // ends by k + 1 == depth at the latest
+      if ((int)k < cap) {
+        if (tuples) M::to_tuple(s, tuples + (size_t)k * M::TUPLE_WORDS);
+        if (actions) actions[k] = action;
+      }
+      typename M::State x;
+      const SimStep r = sim_step<M>(s, k, key, f, depth, cfg->check_deadlock, x);
+      if (r.kind != SIM_RUNNING) {
+        if (kind_out) *kind_out = r.kind;
+        return (int)k + 1;
+      }
+      action = r.info;
+      s = x;
+    }
   });
 }
 

@@ -10,6 +10,9 @@ KubeAPI.toolbox/Model_1, MC.out:2-5):
                           inputs (MC.cfg / MC.tla), reporting the same counts
                           (MC.out:1098), depth (:1101), per-action coverage
                           (:78-621) and counterexample traces.
+* :class:`Simulator`    — tlc2.TLC -simulate: seeded random behaviours on the GPU,
+                          each state checked like the BFS's; the reported walk
+                          is replayed on the host (:meth:`Spec.sim_replay`).
 * :mod:`kubecheck.tlc`  — TLC-style command line (``-config MC.cfg MC``) with
                           ``-tool`` message output.
 
@@ -23,11 +26,12 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import (ACTIONS, ERR_KINDS, INVARIANTS, KcModelConfig, KcResult, KcSqueueConfig,
-                   KcSqueueStats, KubecheckError,
+from ._lib import (ACTIONS, ERR_KINDS, INVARIANTS, SIM_KINDS, KcModelConfig, KcResult, KcSimConfig,
+                   KcSimResult, KcSqueueConfig, KcSqueueStats, KubecheckError,
                    check, load)
 
 __all__ = ["ModelConfig", "ModelChecker", "CheckResult", "FPSet", "StateQueue", "Spec",
+           "Simulator", "SimResult", "SIM_KINDS",
            "KubecheckError", "ACTIONS", "load", "device_count", "stress_fps_dev", "stress_fp"]
 
 
@@ -224,6 +228,108 @@ class ModelChecker:
     def close(self) -> None:
         if self._h:
             self._lib.kc_engine_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@dataclass
+class SimResult:
+    """Result of one simulation run (kc_sim_result)."""
+    steps: int
+    act_steps: Dict[str, int]
+    walks_error: int
+    walks_depth: int
+    walks_terminated: int
+    distinct_visited: int
+    error: Optional[str]              # None, "assertion", "invariant", "deadlock"
+    error_action: Optional[str]
+    error_self: int
+    error_invariant: Optional[str]
+    trace_len: int
+    error_walk: int
+    seconds: float
+    kernel_ms: float
+    launches: int = 0
+    fpset_slots: int = 0
+    trace: List[List[int]] = field(default_factory=list)   # the error walk, replayed on the host
+    trace_actions: List[Optional[str]] = field(default_factory=list)
+    trace_text: str = ""
+
+
+class Simulator:
+    """Simulation mode (TLC's -simulate) on one GPU: `num_walks` seeded random
+    behaviours of at most `depth` states, each state checked against the
+    invariants, the Asserts and deadlock (include/kubecheck.h, "Simulation").
+    The result depends on (model, seed, num_walks, depth) only."""
+
+    def __init__(self, cfg: Optional[ModelConfig] = None, *, seed: int = 0, num_walks: int = 65536,
+                 depth: int = 100, steps_per_launch: int = 0, count_distinct: bool = False,
+                 stop_on_error: bool = False, **kw):
+        self.cfg = cfg or ModelConfig(**kw)
+        self.seed, self.num_walks, self.depth = int(seed) & (2**64 - 1), int(num_walks), int(depth)
+        self._lib = load()
+        self._h = C.c_void_p()
+        self._c = self.cfg.to_c()
+        self._s = KcSimConfig(self.seed, self.num_walks & (2**64 - 1), self.depth, int(steps_per_launch),
+                              int(count_distinct), int(stop_on_error))
+        check("kc_sim_create", self._lib.kc_sim_create(C.byref(self._c), C.byref(self._s), C.byref(self._h)))
+        self.tuple_words = self._lib.kc_spec_tuple_words(self.cfg.nc, self.cfg.np, self.cfg.ns)
+
+    def run(self) -> SimResult:
+        r = KcSimResult()
+        check("kc_sim_run", self._lib.kc_sim_run(self._h, C.byref(r)))
+        res = SimResult(
+            steps=r.steps, act_steps={a: int(r.act_steps[i]) for i, a in enumerate(ACTIONS)},
+            walks_error=r.walks_error, walks_depth=r.walks_depth, walks_terminated=r.walks_terminated,
+            distinct_visited=r.distinct_visited, error=ERR_KINDS.get(r.err_kind),
+            error_action=ACTIONS[r.err_action] if 0 <= r.err_action < len(ACTIONS) else None,
+            error_self=r.err_self, error_invariant=INVARIANTS.get(r.err_invariant),
+            trace_len=r.trace_len, error_walk=r.err_walk, seconds=r.seconds, kernel_ms=r.kernel_ms,
+            launches=r.launches, fpset_slots=r.fpset_slots)
+        if res.error is not None:
+            res.trace, res.trace_actions = self.trace(res.error_walk)
+            n = check("kc_sim_trace_text", self._lib.kc_sim_trace_text(self._h, res.error_walk, None, 0))
+            buf = C.create_string_buffer(n)
+            check("kc_sim_trace_text", self._lib.kc_sim_trace_text(self._h, res.error_walk, buf, n))
+            res.trace_text = buf.value.decode()
+        return res
+
+    def walks(self):
+        """(kind, length, final tuple) of every walk of the last run, as numpy
+        arrays; kinds are _lib.SIM_KINDS' keys."""
+        kind = np.zeros(self.num_walks, dtype=np.uint32)
+        length = np.zeros(self.num_walks, dtype=np.uint32)
+        final = np.zeros((self.num_walks, self.tuple_words), dtype=np.uint64)
+        u32 = C.POINTER(C.c_uint32)
+        check("kc_sim_walks", self._lib.kc_sim_walks(self._h, kind.ctypes.data_as(u32),
+                                                     length.ctypes.data_as(u32), _u64(final)))
+        return kind, length, final
+
+    def trace(self, walk: int):
+        """The behaviour of `walk`, replayed on the host and checked against the
+        device's record: (states as canonical tuples, the action that led to
+        each; None for the Init state)."""
+        walk = int(walk)
+        n = check("kc_sim_trace", self._lib.kc_sim_trace(self._h, walk, None, None, 0))
+        out = np.zeros((n, self.tuple_words), dtype=np.uint64)
+        acts = (C.c_int * n)()
+        check("kc_sim_trace", self._lib.kc_sim_trace(self._h, walk, _u64(out), acts, n))
+        return [[int(x) for x in row] for row in out], [ACTIONS[a] if a >= 0 else None for a in acts]
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.kc_sim_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -507,6 +613,29 @@ class Spec:
         full one; 0 expected."""
         t = np.ascontiguousarray(tup, dtype=np.uint64)
         return check("kc_spec_fp_selfcheck", self._lib.kc_spec_fp_selfcheck(C.byref(self._c), _u64(t)))
+
+    @staticmethod
+    def sim_rand(seed: int, walk: int, k: int) -> int:
+        """r(walk, k) of the simulation RNG (kc_sim_rand)."""
+        return int(load().kc_sim_rand(seed & (2**64 - 1), walk & (2**64 - 1), k & (2**64 - 1)))
+
+    @staticmethod
+    def sim_pick(r: int, n: int) -> int:
+        """floor(r * n / 2^64) (kc_sim_pick)."""
+        return int(load().kc_sim_pick(r & (2**64 - 1), n))
+
+    def sim_replay(self, seed: int, depth: int, walk: int):
+        """One simulated walk on the host (kc_sim_replay; no GPU): (states as
+        canonical tuples, the action that led to each (None for Init), how it
+        ended: a value of SIM_KINDS)."""
+        kind = C.c_int()
+        n = check("kc_sim_replay", self._lib.kc_sim_replay(C.byref(self._c), seed & (2**64 - 1), depth, walk,
+                                                           None, None, 0, C.byref(kind)))
+        out = np.zeros((n, self.tuple_words), dtype=np.uint64)
+        acts = (C.c_int * n)()
+        check("kc_sim_replay", self._lib.kc_sim_replay(C.byref(self._c), seed & (2**64 - 1), depth, walk,
+                                                       _u64(out), acts, n, C.byref(kind)))
+        return out, [ACTIONS[a] if a >= 0 else None for a in acts], SIM_KINDS[kind.value]
 
     def pack(self, tup) -> np.ndarray:
         t = np.ascontiguousarray(tup, dtype=np.uint64)

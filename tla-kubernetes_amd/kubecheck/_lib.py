@@ -67,6 +67,26 @@ class KcResult(C.Structure):
     ]
 
 
+KC_SIM_MAX_DEPTH = 65535
+# how a simulated walk ended (kc_sim_walks / kc_sim_replay): ERR_KINDS' 1-3, then
+SIM_KINDS = {0: "running", 1: "assertion", 2: "invariant", 3: "deadlock", 4: "depth", 5: "terminated"}
+
+
+class KcSimConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("num_walks", C.c_uint64), ("depth", C.c_int),
+                ("steps_per_launch", C.c_int), ("count_distinct", C.c_int), ("stop_on_error", C.c_int)]
+
+
+class KcSimResult(C.Structure):
+    _fields_ = [("steps", C.c_uint64), ("act_steps", C.c_uint64 * KC_NACTIONS),
+                ("walks_error", C.c_uint64), ("walks_depth", C.c_uint64), ("walks_terminated", C.c_uint64),
+                ("distinct_visited", C.c_uint64),
+                ("err_kind", C.c_int), ("err_action", C.c_int), ("err_self", C.c_int),
+                ("err_invariant", C.c_int), ("trace_len", C.c_int), ("err_walk", C.c_uint64),
+                ("seconds", C.c_double), ("kernel_ms", C.c_double),
+                ("launches", C.c_uint64), ("fpset_slots", C.c_uint64)]
+
+
 class KcSqueueConfig(C.Structure):
     _fields_ = [
         ("state_words", C.c_int), ("device", C.c_int), ("segment_states", C.c_uint64),
@@ -185,6 +205,16 @@ SIGNATURES = [
                                     C.c_uint64, _U64P, C.c_uint64, _U64P]),
     ("kc_probe_selftest", C.c_int, [C.c_int, C.c_uint64, _U64P, _U64P, C.c_uint64, C.c_uint32, C.c_int, _U64P,
                            _U64P, _U64P]),
+    ("kc_sim_create", C.c_int, [C.POINTER(KcModelConfig), C.POINTER(KcSimConfig), C.POINTER(_P)]),
+    ("kc_sim_destroy", None, [_P]),
+    ("kc_sim_run", C.c_int, [_P, C.POINTER(KcSimResult)]),
+    ("kc_sim_walks", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _U64P]),
+    ("kc_sim_trace", C.c_int, [_P, C.c_uint64, _U64P, _IP, C.c_int]),
+    ("kc_sim_trace_text", C.c_int64, [_P, C.c_uint64, C.c_char_p, C.c_size_t]),
+    ("kc_sim_rand", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
+    ("kc_sim_pick", C.c_uint64, [C.c_uint64, C.c_uint64]),
+    ("kc_sim_replay", C.c_int, [C.POINTER(KcModelConfig), C.c_uint64, C.c_int, C.c_uint64, _U64P, _IP, C.c_int,
+                                _IP]),
     ("kc_spec_tuple_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_state_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_init", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_int]),

@@ -1,7 +1,8 @@
 """TLC-style command line for the KubeAPI model checker.
 
     python -m kubecheck.tlc [-config MC.cfg] [-deadlock] [-tool] [-nc N -np N -ns N]
-                            [-variant V] [-workers N] [-fp K] [MC]
+                            [-variant V] [-workers N] [-fp K]
+                            [-simulate [num=N]] [-depth D] [-seed S] [-continue] [MC]
 
 Reads the same inputs as the reference's toolbox run: a TLC model config
 (KubeAPI.toolbox/Model_1/MC.cfg:1-16 — CONSTANT assignments, either direct
@@ -16,6 +17,22 @@ produced (no TLA+ front end).  The model check itself
 runs on the GPU (kubecheck.ModelChecker); -workers and -fp are accepted for
 command-line compatibility (the GPU replaces the worker pool; fingerprints
 are kubecheck's own 64-bit hash, not TLC's FP64 #K).
+
+Simulation mode (TLC's -simulate): with `-simulate [num=N]` a
+kubecheck.Simulator runs instead of the ModelChecker: N seeded random
+behaviours of at most `-depth D` states (default 100, TLC's), each state
+checked against the invariants, the Asserts and deadlock.  `-seed S` makes the
+run reproducible (default: from the clock); the run stops at the first launch
+in which a behaviour errs unless `-continue` is given.  It prints a start
+banner naming the seed, the walks and the depth; on an error the violation
+message (2110/2132/2114), 2121 and the 2217 states of the behaviour, replayed
+on the host; the coverage block with the steps taken per action in the place
+of both counts; a totals line; 2186.  The exit code is 12 on an error, as for
+the BFS.  Differences from TLC: N defaults to 65,536 behaviours (TLC's
+-simulate runs until it is stopped), the random stream is kubecheck's own
+(no -aril), and the reference holds no simulation output, so the
+simulate-specific message bodies and codes claim no match with TLC's.
+Without -simulate nothing changes.
 """
 from __future__ import annotations
 
@@ -223,8 +240,83 @@ def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = 
     return out
 
 
-def main(argv: Optional[List[str]] = None) -> int:
+SIM_DEFAULT_WALKS = 65536   # TLC's -simulate runs until stopped; kubecheck needs a bound
+SIM_DEFAULT_DEPTH = 100     # TLC's -depth default
+
+
+def sim_messages(r, num_init: int, seed: int, num_walks: int, depth: int, t_start: float, t_end: float,
+                 engine: str = "") -> List[tuple]:
+    """-tool messages (code, class, body) for one simulation run.  The
+    violation reports (2110/2132/2114, 2121, 2217) and the coverage block
+    (2201/2773/2772/2202, the steps per action in the place of both counts)
+    have the bodies the BFS prints.  The simulate-specific lines (the 2187
+    start banner, the 2210 totals line: their codes and their wording) are
+    kubecheck's own: the reference holds no simulation output, so nothing here
+    claims to match what TLC prints in this mode."""
+    out = []
+    add = lambda code, text, cls=0: out.append((code, cls, text))  # noqa: E731
+    add(2262, f"kubecheck (simulation mode) {engine}".rstrip())
+    add(2187, f"Running Random Simulation with seed {seed}: {num_walks} behaviors of at most {depth} states "
+              f"on 1 MI355X GPU.")
+    add(2185, f"Starting... ({tstamp(t_start)})")
+    if r.error is not None:
+        if r.error == "invariant":
+            add(2110, f"Invariant {r.error_invariant} is violated.", 1)
+        elif r.error == "assertion":
+            add(2132, f"The first argument of Assert evaluated to FALSE (action {r.error_action}).", 1)
+        else:
+            add(2114, "Deadlock reached.", 1)
+        add(2121, "The behavior up to this point is:", 1)
+        blocks = re.split(r"^State (\d+):$", r.trace_text, flags=re.M)[1:]
+        for num, body in zip(blocks[0::2], blocks[1::2]):
+            add(2217, f"{num}: {body.strip()}", 4)
+    add(2201, f"The coverage statistics at {tstamp(t_end)}")
+    add(2773, f"{span_text('Init', INIT_SPAN)}: {num_init}:{num_init}")
+    for name, span in ACTION_SPANS.items():
+        add(2772, f"{span_text(name, span)}: {r.act_steps[name]}:{r.act_steps[name]}")
+    add(2202, "End of statistics.")
+    line = (f"{r.steps} steps taken in {num_walks} behaviors (walk {r.error_walk} is the one reported): "
+            if r.error is not None else f"{r.steps} steps taken in {num_walks} behaviors: ")
+    line += (f"{r.walks_error} ended in an error, {r.walks_depth} at the depth limit, "
+             f"{r.walks_terminated} terminated")
+    if r.fpset_slots:
+        line += f"; {r.distinct_visited} distinct states visited"
+    add(2210, line + ".")
+    add(2186, f"Finished in {int(round((t_end - t_start) * 1000))}ms at ({tstamp(t_end)})")
+    return out
+
+
+def split_simulate(argv: List[str]):
+    """Take TLC's `-simulate [num=N]` out of argv: (rest, simulate?, N or None).
+    The optional argument is TLC's comma-separated list; only num= is known."""
+    rest, sim, num = [], False, None
+    i = 0
+    while i < len(argv):
+        if argv[i] != "-simulate":
+            rest.append(argv[i])
+            i += 1
+            continue
+        sim = True
+        i += 1
+        if i < len(argv) and "=" in argv[i] and not argv[i].startswith("-"):
+            for item in argv[i].split(","):
+                m = re.fullmatch(r"num=(\d+)", item)
+                if not m or int(m.group(1)) < 1:
+                    raise CfgError(f"-simulate {argv[i]}: expected num=N with N >= 1")
+                num = int(m.group(1))
+            i += 1
+    return rest, sim, num
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    argv, simulate, num = split_simulate(argv)
     ap = argparse.ArgumentParser(prog="kubecheck.tlc", description=__doc__.split("\n\n")[0])
+    ap.add_argument("-depth", type=int, default=SIM_DEFAULT_DEPTH,
+                    help="-simulate: the most states in a behaviour (TLC's default 100)")
+    ap.add_argument("-seed", type=int, default=None, help="-simulate: RNG seed (default: from the clock)")
+    ap.add_argument("-continue", dest="cont", action="store_true",
+                    help="-simulate: run every behaviour to its end after an error")
     ap.add_argument("spec", nargs="?", default="MC")
     ap.add_argument("-config", default=None)
     ap.add_argument("-deadlock", action="store_true", help="do NOT check for deadlock (TLC flag)")
@@ -239,6 +331,18 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("-nocheckfps", action="store_true",
                     help="skip the 'based on the actual fingerprints' estimate (a sort of the seen-set)")
     a = ap.parse_args(argv)
+    a.simulate, a.num = simulate, (num if num is not None else SIM_DEFAULT_WALKS)
+    if simulate and not 1 <= a.depth <= 65535:
+        raise CfgError(f"-depth {a.depth}: expected 1..65535")
+    return a
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    try:
+        a = parse_args(argv)
+    except CfgError as e:
+        print(f"Error: {e}", file=sys.stderr)
+        return 1
 
     cfg_path = a.config or f"{a.spec}.cfg"
     if not os.path.exists(cfg_path):
@@ -253,6 +357,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     mc_cfg = kubecheck.ModelConfig(nc=a.nc, np=a.np, ns=a.ns, variant=a.variant, device=a.device,
                                    check_deadlock=not a.deadlock, **kw)
     t0 = time.time()
+    if a.simulate:
+        seed = a.seed if a.seed is not None else time.time_ns()
+        with kubecheck.Simulator(mc_cfg, seed=seed, num_walks=a.num, depth=a.depth, count_distinct=True,
+                                 stop_on_error=not a.cont) as sim:
+            r = sim.run()
+            seed = sim.seed
+        num_init = len(kubecheck.Spec(mc_cfg).init())
+        for code, cls, body in sim_messages(r, num_init, seed, a.num, a.depth, t0, t0 + r.seconds,
+                                            kubecheck.load().kc_build_info().decode()):
+            print(msg(code, body, cls, a.tool), flush=True)
+        return 0 if r.error is None else 12
     with kubecheck.ModelChecker(mc_cfg) as mc:
         r = mc.run()
         prob = None if (a.nocheckfps or r.error is not None) else mc.check_fps()[1]
