@@ -613,6 +613,51 @@ void kc_coldset_destroy(void *h);
 int kc_spill_selftest(int kind, int np, const uint64_t *a, uint64_t na, const uint64_t *b, uint64_t nb,
                       const uint64_t *c, uint64_t nc, uint64_t cap, uint64_t *out, uint64_t nout, uint64_t *res);
 
+/* ------------------------------ Scan, emit and rebuild of a wide level (tests) */
+/* One launch of a kernel that turns a wide level's newmask words into the
+ * next frontier (csrc/engine_kernels.h), with the engine's grid and block
+ * sizes (csrc/emit_selftest.hip).  par = the kind's npar scalars; a, b =
+ * inputs; out = the output sections, res = counters.  Everything travels as
+ * u64 words, one per element.  Each output section is uploaded as given and
+ * copied back whole: KC_EMIT_FORE guard elements, the kernel's array, the
+ * caller's aft guards.  Every index a kernel derives from its input is checked
+ * on the host first, and every section must hold the worst case the input
+ * allows (-EINVAL, with or without a GPU).  cfg is read by kinds 3 and 4 only
+ * (nc = ns = 1, np 1 or 2; variant, invariants and the constants apply).
+ * 0 k_tile_scan / k_chunk_scan: par = [T, reg_ok, chunk]; a = the
+ *   4 * ceil(T / 4) cells the scan loads (pad cells: anything; the first T sum
+ *   below 2^32); out = off, max(4 * ceil(T / 4), T + 1) cells at least;
+ *   res = the na input cells after the launch.
+ * 1 tile_scan_body with ScanMarks: par = [T, reg_ok, stride, nmark <= 16,
+ *   extra (0xffffffff: none)]; a, out as kind 0; res = sh_mark[0 .. 16], each
+ *   0xA5A5A5A5 before the scan.
+ * 2 k_emit_links: par = [n, base, level_gidx, next_gidx, cap, chunk_base, mode,
+ *   want_link, want_trace, seclen]; a = newmask[n]; b = tile_off[T + 1] (mode 0;
+ *   T = ceil(n / 256)) or coff[ceil(T / 64) + 1] then ttot[T] (mode 1), which
+ *   must be the masks' exclusive sums and counts; out = link, parent, ord:
+ *   seclen elements each, KC_EMIT_FORE + next_gidx + chunk_base + total + 1 at
+ *   least; res = [defer_flags, outdeg[16]].
+ * 3 k_emit<M>: par = [n, base, next_base, chunk_base, level_gidx, next_gidx,
+ *   keep_trace, mode, seclen_next, seclen_trace]; a = n packed parents raising
+ *   no Assert; b = newmask[n], bits below each parent's successor count; mode 0
+ *   tile offsets, 1 per-parent offsets (the harness's own sums); out = next
+ *   (seclen_next states >= KC_EMIT_FORE + chunk_base - next_base + total), then
+ *   parent and ord (seclen_trace >= KC_EMIT_FORE + next_gidx + chunk_base +
+ *   total each); res = [err_key, next_cand, act_dist[22], outdeg[16]].
+ * 4 k_materialize<M>: par = [n, nprev, mode, gidx0, prev_gidx0, prev_counts];
+ *   a = nprev packed states; b = link[n] (mode 0: parent << 8 | position) or
+ *   parent[n] then ord[n] (mode 1: global indices, read at gidx0 + i); parents
+ *   inside the previous frontier, positions below the parent's successor
+ *   count; out = KC_EMIT_FORE + n states at least; res = [defer_flags,
+ *   defer_inv_n, next_cand, act_dist[22]].
+ * 5 k_parent_chain: par = [g, cap]; a = parent[na] (below na, or ~0), b =
+ *   ord[na]; out (pinned host memory) = guards, the length, cap chain words.
+ * 6 spread_tile: par = [G, S]; out[b] = spread_tile(b, G, S), b < G. */
+#define KC_EMIT_FORE 8
+int kc_emit_selftest(int kind, const kc_model_config *cfg, const uint64_t *par, uint64_t npar, const uint64_t *a,
+                     uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *out, uint64_t nout, uint64_t *res,
+                     uint64_t nres);
+
 /* ------------------------------------------------- Probe primitives (tests) */
 /* Device harness for the seen-set probe loops (csrc/probe_selftest.hip): runs
  * n operations of one kind through the product's device functions on a table

@@ -18,26 +18,15 @@
 #include "fpset_host.h"
 #include "kc_common.h"
 #include "kubeapi_spec.h"
+#include "selftest_util.h"
 
 namespace kc {
 namespace {
 
+using selftest::DevBuf;
+using selftest::upload;
+
 constexpr uint64_t kSpillTestMax = 1ull << 20;    // slots, parents, queries
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-int upload(DevBuf& d, const void* src, uint64_t bytes) {
-  KC_HIP_TRY(hipMalloc(&d.p, bytes ? bytes : 8));
-  if (bytes) KC_HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
 
 int bad(const char* what) {
   set_error("kc_spill_selftest: %s", what);
@@ -50,26 +39,11 @@ Flags test_flags() {
   return flags_of(c);
 }
 
-// The packed states are states of the lowered domain (they survive the round
-// trip through the canonical tuple); tot[i] = successors of state i, capped
-// like the kernels cap them.
+// (selftest_util.h check_states under the default flags)
 template <class M>
 int check_states(const uint64_t* packed, uint64_t n, std::vector<int>& tot) {
-  const Flags f = test_flags();
-  tot.resize(n);
-  for (uint64_t i = 0; i < n; ++i) {
-    typename M::State s, r;
-    for (int k = 0; k < M::W; ++k) s.w[k] = packed[i * M::W + k];
-    uint64_t tup[M::TUPLE_WORDS];
-    M::to_tuple(s, tup);
-    bool same = M::from_tuple(tup, r);
-    for (int k = 0; same && k < M::W; ++k) same = r.w[k] == s.w[k];
-    if (!same) return bad("a parent is not a packed state of the model");
-    const typename M::Plan pl = M::plan(s, f);
-    if (pl.fail_pos >= 0) return bad("a parent raises an Assert failure");
-    tot[i] = pl.total > M::MAXSUCC ? M::MAXSUCC : pl.total;
-  }
-  return 0;
+  const char* why = selftest::check_states<M>(packed, n, test_flags(), tot);
+  return why ? bad(why) : 0;
 }
 
 // kind 0.  a = table image (2 words per slot), na = slots; out = nout >= cap

@@ -203,6 +203,8 @@ SIGNATURES = [
     ("kc_coldset_destroy", None, [_P]),
     ("kc_spill_selftest", C.c_int, [C.c_int, C.c_int, _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64,
                                     C.c_uint64, _U64P, C.c_uint64, _U64P]),
+    ("kc_emit_selftest", C.c_int, [C.c_int, C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P,
+                                   C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64]),
     ("kc_probe_selftest", C.c_int, [C.c_int, C.c_uint64, _U64P, _U64P, C.c_uint64, C.c_uint32, C.c_int, _U64P,
                            _U64P, _U64P]),
     ("kc_sim_create", C.c_int, [C.POINTER(KcModelConfig), C.POINTER(KcSimConfig), C.POINTER(_P)]),
