@@ -37,6 +37,9 @@
  *   kc_sim_*     tlc2.TLC -simulate: bounded random behaviours checked
  *                against the same invariants, Asserts and deadlock (the
  *                reference holds no simulation run; semantics below).
+ *   kc_live_*    tlc2.TLC's liveness check of the spec's temporal properties
+ *                under WF_vars(Next) (the reference holds no liveness output;
+ *                semantics below).
  *   kc_spec_*    host-side access to the lowered spec (canonical tuples) —
  *                used for trace replay and by the parity tests.
  */
@@ -547,6 +550,86 @@ uint64_t kc_sim_pick(uint64_t r, uint64_t n);
  * returns the number of states. */
 int kc_sim_replay(const kc_model_config *cfg, uint64_t seed, int depth, uint64_t walk,
                   uint64_t *tuples_out, int *actions_out, int cap, int *kind_out);
+
+/* ------------------------------------------------------------ Liveness */
+/* KubeAPI.tla's temporal properties (ReconcileCompletes :798,
+ * CleansUpProperly :806) on one GPU, under
+ *   Spec == Init /\ [][Next]_vars /\ WF_vars(Next)                 (:765).
+ *
+ * Each property reduces to one question about a state predicate `stay`: is
+ * there a behaviour of Spec that reaches a stay state and remains in stay
+ * states for ever?
+ *   0 ReconcileCompletes  sR ~> ~sR          stay = shouldReconcile[Client]
+ *   1 CleansUpProperly    []~sR ~> no Secret/foo in apiState
+ *                                            stay = ~sR /\ apiState holds a
+ *                                                   version of Secret/foo
+ *   2 ClientRestarts      []<>(pc[Client] = "CStart")   (build-defined)
+ *                                            stay = pc[Client] # "CStart"
+ *   3 SomeActorRestarts   []<>(some client is at CStart or some controller at
+ *                         PVCStart)                     (build-defined)
+ *                                            stay = no actor is at its start
+ * 2 and 3 are not in KubeAPI.tla (as NoLostUpdate is not among its
+ * invariants): on this spec 0 and 1 never make the elimination remove a state,
+ * and these two do.  0-2 speak of the one client: nc must be 1 (-EINVAL).
+ *
+ * Weak fairness of Next as a whole only forbids stuttering for ever while a
+ * step that changes vars is enabled.  On the finite reachable graph, with the
+ * edges s -> s dropped (they are not <Next>_vars steps): s is terminal if it
+ * has no successor other than itself, and L is the largest set of reachable
+ * stay states in which every state is terminal or has a successor in L.  The
+ * property is violated iff L is not empty.  L is computed by elimination:
+ * alive = stay, then rounds in which an alive, non-terminal state with no alive
+ * successor other than itself dies, until a round removes nothing (one-pass
+ * OWCTY without the SCC step; exact for this single fairness condition, not
+ * for per-process fairness).
+ *
+ * The counterexample is a shortest behaviour from an Init state to the L state
+ * with the smallest (BFS level, discovery index), then from that state the
+ * first alive successor other than itself, in kc_spec_successors order, until
+ * the walk meets a state it has visited (kind 1, TLC's "Back to state") or a
+ * terminal state (kind 2, TLC's "Stuttering").
+ *
+ * The graph is built by a BFS of the checker's own (the engine is not
+ * involved); the invariants are not evaluated.  A state whose Next raises an
+ * Assert ends the build: err_kind = 1 and no verdict (kc_engine_* is the tool
+ * for safety).  max_states sizes every buffer at create (the edge buffer holds
+ * 8 per state); a larger graph ends kc_live_run with -ENOMEM. */
+typedef struct {
+  int property;              /* 0 .. 3, above */
+  uint64_t max_states;       /* 0 = 2^24; 16 .. 2^27 */
+} kc_live_config;
+typedef struct {
+  uint64_t states, edges, init; /* the graph: the BFS's distinct, generated - init */
+  int depth;                    /* ... and depth */
+  uint64_t stay_states, live_states, live_terminal; /* |S|, |L|, terminal states in L */
+  uint64_t rounds;              /* trim launches, the last (empty) one included */
+  int err_kind, err_action, err_self; /* an Assert met while building the graph */
+  int violated;                 /* 1 iff |L| > 0 */
+  int kind;                     /* 0 none, 1 back-to-state, 2 stuttering */
+  int prefix_len;               /* states up to and including the first L state */
+  int trace_len, loop_start;    /* states in the counterexample; 0-based index the last
+                                   state steps back to, -1 if stuttering */
+  double seconds, build_ms, trim_ms; /* host wall time: the run, the graph build, mark and trim */
+} kc_live_result;
+typedef struct kc_live kc_live;
+/* Model validation and errors as kc_sim_create (-EINVAL, -ENODEV without a
+ * GPU, -ENOMEM); the BFS-only fields of the model config are ignored. */
+int kc_live_create(const kc_model_config *cfg, const kc_live_config *live, kc_live **out);
+void kc_live_destroy(kc_live *l);
+int kc_live_run(kc_live *l, kc_live_result *res);
+/* The counterexample of the last run: up to `cap` states as canonical tuples
+ * and the action that led to each (-1 for the Init state); returns the number
+ * of states (0 if the property holds). */
+int kc_live_trace(kc_live *l, uint64_t *tuples_out, int *actions_out, int cap);
+/* The same as TLC-style text ("State 1: ..."); returns bytes needed or < 0. */
+int64_t kc_live_trace_text(kc_live *l, char *buf, size_t cap);
+/* Every state of the last run's graph, in discovery order, with its final
+ * alive bit (1 = in L); for the tests.  Returns the number of states; nothing
+ * is written if cap is smaller. */
+int kc_live_alive(kc_live *l, uint64_t *tuples_out, uint8_t *alive_out, uint64_t cap);
+/* stay(tuple) of a property on the host (no GPU), through the code the kernels
+ * run: 1 / 0, < 0 on error. */
+int kc_live_stay(const kc_model_config *cfg, int property, const uint64_t *tuple);
 
 /* ----------------------------------------------- Seen-set spill (tests) */
 /* Host self-check of the cold tier's run search (coldset.hip run_find, the

@@ -13,6 +13,9 @@ KubeAPI.toolbox/Model_1, MC.out:2-5):
 * :class:`Simulator`    — tlc2.TLC -simulate: seeded random behaviours on the GPU,
                           each state checked like the BFS's; the reported walk
                           is replayed on the host (:meth:`Spec.sim_replay`).
+* :class:`LivenessChecker` — tlc2.TLC's liveness check of the spec's temporal
+                          properties under WF_vars(Next): the reachable graph,
+                          the elimination and a lasso counterexample on the GPU.
 * :mod:`kubecheck.tlc`  — TLC-style command line (``-config MC.cfg MC``) with
                           ``-tool`` message output.
 
@@ -26,12 +29,13 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import (ACTIONS, ERR_KINDS, INVARIANTS, SIM_KINDS, KcModelConfig, KcResult, KcSimConfig,
+from ._lib import (ACTIONS, ERR_KINDS, INVARIANTS, LIVE_KINDS, PROPERTIES, SIM_KINDS, KcLiveConfig,
+                   KcLiveResult, KcModelConfig, KcResult, KcSimConfig,
                    KcSimResult, KcSqueueConfig, KcSqueueStats, KubecheckError,
                    check, load)
 
 __all__ = ["ModelConfig", "ModelChecker", "CheckResult", "FPSet", "StateQueue", "Spec",
-           "Simulator", "SimResult", "SIM_KINDS",
+           "Simulator", "SimResult", "SIM_KINDS", "LivenessChecker", "LiveResult", "PROPERTIES",
            "KubecheckError", "ACTIONS", "load", "device_count", "stress_fps_dev", "stress_fp"]
 
 
@@ -345,6 +349,107 @@ class Simulator:
             pass
 
 
+@dataclass
+class LiveResult:
+    """Result of one liveness check (kc_live_result)."""
+    property: str
+    states: int                       # the reachable graph: the BFS's distinct,
+    edges: int                        # ... generated - init
+    init: int
+    depth: int
+    stay_states: int                  # |S|
+    live_states: int                  # |L|
+    live_terminal: int                # terminal states in L
+    rounds: int                       # trim launches, the last (empty) one included
+    error: Optional[str]              # None, or "assertion": met while building the graph, no verdict
+    error_action: Optional[str]
+    error_self: int
+    violated: bool
+    kind: Optional[str]               # None, "back-to-state", "stuttering"
+    prefix_len: int
+    trace_len: int
+    loop_start: int                   # 0-based index the last state steps back to; -1 if stuttering
+    seconds: float
+    build_ms: float
+    trim_ms: float
+    trace: List[List[int]] = field(default_factory=list)
+    trace_actions: List[Optional[str]] = field(default_factory=list)
+    trace_text: str = ""
+
+
+class LivenessChecker:
+    """A temporal property of KubeAPI.tla under WF_vars(Next) on one GPU
+    (include/kubecheck.h, "Liveness"): the reachable graph, the elimination of
+    the states no fair behaviour can stay in, and a lasso counterexample.
+    `property` is a name of PROPERTIES or its index."""
+
+    def __init__(self, cfg: Optional[ModelConfig] = None, property="ReconcileCompletes",
+                 max_states: Optional[int] = None, **kw):
+        self.cfg = cfg or ModelConfig(**kw)
+        if isinstance(property, str):
+            if property not in PROPERTIES:
+                raise ValueError(f"unknown property {property!r}; known: {PROPERTIES}")
+            property = PROPERTIES.index(property)
+        self.property = int(property)
+        self._lib = load()
+        self._h = C.c_void_p()
+        self._c = self.cfg.to_c()
+        self._l = KcLiveConfig(self.property, int(max_states or 0))
+        check("kc_live_create", self._lib.kc_live_create(C.byref(self._c), C.byref(self._l), C.byref(self._h)))
+        self.tuple_words = self._lib.kc_spec_tuple_words(self.cfg.nc, self.cfg.np, self.cfg.ns)
+
+    def run(self) -> LiveResult:
+        r = KcLiveResult()
+        check("kc_live_run", self._lib.kc_live_run(self._h, C.byref(r)))
+        res = LiveResult(
+            property=PROPERTIES[self.property], states=r.states, edges=r.edges, init=r.init, depth=r.depth,
+            stay_states=r.stay_states, live_states=r.live_states, live_terminal=r.live_terminal,
+            rounds=r.rounds, error=ERR_KINDS.get(r.err_kind),
+            error_action=ACTIONS[r.err_action] if 0 <= r.err_action < len(ACTIONS) else None,
+            error_self=r.err_self, violated=bool(r.violated), kind=LIVE_KINDS.get(r.kind),
+            prefix_len=r.prefix_len, trace_len=r.trace_len, loop_start=r.loop_start, seconds=r.seconds,
+            build_ms=r.build_ms, trim_ms=r.trim_ms)
+        if res.violated:
+            n = res.trace_len
+            out = np.zeros((n, self.tuple_words), dtype=np.uint64)
+            acts = (C.c_int * n)()
+            check("kc_live_trace", self._lib.kc_live_trace(self._h, _u64(out), acts, n))
+            res.trace = [[int(x) for x in row] for row in out]
+            res.trace_actions = [ACTIONS[a] if a >= 0 else None for a in acts]
+            nb = check("kc_live_trace_text", self._lib.kc_live_trace_text(self._h, None, 0))
+            buf = C.create_string_buffer(nb)
+            check("kc_live_trace_text", self._lib.kc_live_trace_text(self._h, buf, nb))
+            res.trace_text = buf.value.decode()
+        return res
+
+    def alive(self):
+        """Every state of the last run's graph in discovery order (canonical
+        tuples) and its final alive bit (True = in L), as numpy arrays."""
+        n = check("kc_live_alive", self._lib.kc_live_alive(self._h, None, None, 0))
+        tuples = np.zeros((n, self.tuple_words), dtype=np.uint64)
+        bits = np.zeros(n, dtype=np.uint8)
+        check("kc_live_alive", self._lib.kc_live_alive(self._h, _u64(tuples),
+                                                       bits.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return tuples, bits.astype(bool)
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.kc_live_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _stream(stream):
     return C.c_void_p(stream.cuda_stream if stream is not None else 0)
 
@@ -636,6 +741,13 @@ class Spec:
         check("kc_sim_replay", self._lib.kc_sim_replay(C.byref(self._c), seed & (2**64 - 1), depth, walk,
                                                        _u64(out), acts, n, C.byref(kind)))
         return out, [ACTIONS[a] if a >= 0 else None for a in acts], SIM_KINDS[kind.value]
+
+    def stay(self, property, tup) -> bool:
+        """stay(tuple) of a temporal property (a name of PROPERTIES or its
+        index) on the host (kc_live_stay; no GPU)."""
+        prop = PROPERTIES.index(property) if isinstance(property, str) else int(property)
+        t = np.ascontiguousarray(tup, dtype=np.uint64)
+        return bool(check("kc_live_stay", self._lib.kc_live_stay(C.byref(self._c), prop, _u64(t))))
 
     def pack(self, tup) -> np.ndarray:
         t = np.ascontiguousarray(tup, dtype=np.uint64)

@@ -87,6 +87,26 @@ class KcSimResult(C.Structure):
                 ("launches", C.c_uint64), ("fpset_slots", C.c_uint64)]
 
 
+# temporal properties kc_live_* checks (kc_live_config.property = the index)
+PROPERTIES = ("ReconcileCompletes", "CleansUpProperly", "ClientRestarts", "SomeActorRestarts")
+# how a liveness counterexample ends (kc_live_result.kind)
+LIVE_KINDS = {0: None, 1: "back-to-state", 2: "stuttering"}
+
+
+class KcLiveConfig(C.Structure):
+    _fields_ = [("property", C.c_int), ("max_states", C.c_uint64)]
+
+
+class KcLiveResult(C.Structure):
+    _fields_ = [("states", C.c_uint64), ("edges", C.c_uint64), ("init", C.c_uint64), ("depth", C.c_int),
+                ("stay_states", C.c_uint64), ("live_states", C.c_uint64), ("live_terminal", C.c_uint64),
+                ("rounds", C.c_uint64),
+                ("err_kind", C.c_int), ("err_action", C.c_int), ("err_self", C.c_int),
+                ("violated", C.c_int), ("kind", C.c_int), ("prefix_len", C.c_int),
+                ("trace_len", C.c_int), ("loop_start", C.c_int),
+                ("seconds", C.c_double), ("build_ms", C.c_double), ("trim_ms", C.c_double)]
+
+
 class KcSqueueConfig(C.Structure):
     _fields_ = [
         ("state_words", C.c_int), ("device", C.c_int), ("segment_states", C.c_uint64),
@@ -217,6 +237,13 @@ SIGNATURES = [
     ("kc_sim_pick", C.c_uint64, [C.c_uint64, C.c_uint64]),
     ("kc_sim_replay", C.c_int, [C.POINTER(KcModelConfig), C.c_uint64, C.c_int, C.c_uint64, _U64P, _IP, C.c_int,
                                 _IP]),
+    ("kc_live_create", C.c_int, [C.POINTER(KcModelConfig), C.POINTER(KcLiveConfig), C.POINTER(_P)]),
+    ("kc_live_destroy", None, [_P]),
+    ("kc_live_run", C.c_int, [_P, C.POINTER(KcLiveResult)]),
+    ("kc_live_trace", C.c_int, [_P, _U64P, _IP, C.c_int]),
+    ("kc_live_trace_text", C.c_int64, [_P, C.c_char_p, C.c_size_t]),
+    ("kc_live_alive", C.c_int, [_P, _U64P, _U8P, C.c_uint64]),
+    ("kc_live_stay", C.c_int, [C.POINTER(KcModelConfig), C.c_int, _U64P]),
     ("kc_spec_tuple_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_state_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_init", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_int]),

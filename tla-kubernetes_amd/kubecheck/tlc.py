@@ -33,6 +33,20 @@ the BFS.  Differences from TLC: N defaults to 65,536 behaviours (TLC's
 (no -aril), and the reference holds no simulation output, so the
 simulate-specific message bodies and codes claim no match with TLC's.
 Without -simulate nothing changes.
+
+Temporal properties: a cfg with a PROPERTY list (models/Liveness.cfg; the names
+of kubecheck.PROPERTIES: KubeAPI.tla's ReconcileCompletes and CleansUpProperly,
+and the build-defined ClientRestarts and SomeActorRestarts) first runs the BFS
+exactly as without it.  If that ends without an error, each property is
+checked in cfg order by a kubecheck.LivenessChecker under WF_vars(Next)
+(include/kubecheck.h, "Liveness"), a 2192 line naming it, between the BFS
+block and its closing 2186.  The first violation is reported and ends the run:
+2116 "Temporal properties were violated.", 2264 "The following behavior
+constitutes a counter-example:", the 2217 states, then 2122 "Back to state N"
+or 2218 "Stuttering"; the exit code is 13.  The reference holds no liveness
+output, so these codes and their wording claim no match with TLC's.
+-simulate together with a PROPERTY list is an error.  Without a PROPERTY list
+nothing changes.
 """
 from __future__ import annotations
 
@@ -129,6 +143,21 @@ def model_from_cfg(cfg: dict) -> dict:
         (2 if "OnlyOneVersion" in cfg["invariants"] else 0) | \
         (4 if "NoLostUpdate" in cfg["invariants"] else 0)
     return kw
+
+
+def check_from_cfg(cfg: dict, simulate: bool = False):
+    """model_from_cfg for a cfg that may list temporal properties: (ModelConfig
+    kwargs, the PROPERTY names in cfg order).  The names must be kubecheck's
+    PROPERTIES; simulation mode checks none."""
+    from ._lib import PROPERTIES
+
+    props = list(cfg["properties"])
+    bad = [x for x in props if x not in PROPERTIES]
+    if bad:
+        raise CfgError(f"unknown temporal property(ies) {bad}; known: {PROPERTIES}")
+    if props and simulate:
+        raise CfgError("-simulate checks no temporal PROPERTY (liveness needs the whole state graph)")
+    return model_from_cfg(dict(cfg, properties=[])), props
 
 
 def msg(code: int, text: str, cls: int = 0, tool: bool = True) -> str:
@@ -286,6 +315,26 @@ def sim_messages(r, num_init: int, seed: int, num_walks: int, depth: int, t_star
     return out
 
 
+def live_messages(r) -> List[tuple]:
+    """-tool messages (code, class, body) for a violated temporal property (a
+    kubecheck.LiveResult): 2116, 2264, the 2217 states of the counterexample,
+    then 2122 "Back to state N" or 2218 "Stuttering".  The reference holds no
+    liveness output, so these codes and their wording claim no match with
+    TLC's."""
+    out = []
+    add = lambda code, text, cls=0: out.append((code, cls, text))  # noqa: E731
+    add(2116, "Temporal properties were violated.", 1)
+    add(2264, "The following behavior constitutes a counter-example:", 1)
+    blocks = re.split(r"^State (\d+):$", r.trace_text, flags=re.M)[1:]
+    for num, body in zip(blocks[0::2], blocks[1::2]):
+        add(2217, f"{num}: {body.strip()}", 4)
+    if r.kind == "back-to-state":
+        add(2122, f"{r.trace_len + 1}: Back to state {r.loop_start + 1}", 4)
+    else:
+        add(2218, f"{r.trace_len + 1}: Stuttering", 4)
+    return out
+
+
 def split_simulate(argv: List[str]):
     """Take TLC's `-simulate [num=N]` out of argv: (rest, simulate?, N or None).
     The optional argument is TLC's comma-separated list; only num= is known."""
@@ -350,7 +399,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 1
     tla_path = os.path.join(os.path.dirname(os.path.abspath(cfg_path)), f"{a.spec}.tla")
     defs = parse_defs(open(tla_path).read()) if os.path.exists(tla_path) else {}
-    kw = model_from_cfg(parse_cfg(open(cfg_path).read(), defs))
+    kw, props = check_from_cfg(parse_cfg(open(cfg_path).read(), defs), a.simulate)
 
     import kubecheck
 
@@ -372,10 +421,32 @@ def main(argv: Optional[List[str]] = None) -> int:
         r = mc.run()
         prob = None if (a.nocheckfps or r.error is not None) else mc.check_fps()[1]
     t1 = t0 + r.seconds
-    for code, cls, body in messages(r, t0, t1, prob, kubecheck.load().kc_build_info().decode(),
-                                    kubecheck.device_count()):
+    out = messages(r, t0, t1, prob, kubecheck.load().kc_build_info().decode(), kubecheck.device_count())
+    if not props or r.error is not None:
+        for code, cls, body in out:
+            print(msg(code, body, cls, a.tool), flush=True)
+        return 0 if r.error is None else 12
+    # temporal properties, in cfg order, between the BFS block and its 2186 line
+    for code, cls, body in out[:-1]:
         print(msg(code, body, cls, a.tool), flush=True)
-    return 0 if r.error is None else 12
+    rc = 0
+    for name in props:
+        print(msg(2192, f"Checking temporal property {name} for the complete state space with {r.distinct} "
+                        f"total distinct states at ({tstamp(time.time())})", 0, a.tool), flush=True)
+        with kubecheck.LivenessChecker(mc_cfg, name) as lc:
+            lr = lc.run()
+        t1 += lr.seconds
+        if lr.error is not None or (lr.states, lr.edges) != (r.distinct, r.generated - r.init):
+            print(f"Error: the liveness graph ({lr.states} states, {lr.edges} edges, error {lr.error}) is not "
+                  f"the BFS's ({r.distinct}, {r.generated - r.init})", file=sys.stderr)
+            return 1
+        if lr.violated:
+            for code, cls, body in live_messages(lr):
+                print(msg(code, body, cls, a.tool), flush=True)
+            rc = 13
+            break
+    print(msg(2186, f"Finished in {int(round((t1 - t0) * 1000))}ms at ({tstamp(t1)})", 0, a.tool), flush=True)
+    return rc
 
 
 if __name__ == "__main__":

@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""Timings of the liveness check (kubecheck.LivenessChecker) on one GPU.
+
+    python tools/live_bench.py [--reps 3] [--json OUT.json] [--md OUT.md]
+
+For Model_1 and for NP=2 with both constants FALSE, every property: the size of
+the graph, |S| and |L|, the trim rounds, and build_ms (the graph build), trim_ms
+(mark and trim) and the whole run's wall time, each the best of --reps runs
+after one warm-up run on the same handle.  Writes one JSON document and the
+table of DESIGN.md §7.12.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tla-kubernetes_amd"))
+
+MODELS = [("Model_1", dict()), ("NP=2, constants FALSE", dict(np=2, can_fail=False, can_timeout=False))]
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--md", default=None)
+    a = ap.parse_args()
+
+    import kubecheck
+
+    if kubecheck.device_count() < 1:
+        print("live_bench: no GPU visible", file=sys.stderr)
+        return 1
+    doc = {"what": "liveness check timings", "reps": a.reps,
+           "build": kubecheck.load().kc_build_info().decode(), "runs": []}
+    for name, flags in MODELS:
+        for prop in kubecheck.PROPERTIES:
+            with kubecheck.LivenessChecker(kubecheck.ModelConfig(**flags), prop) as lc:
+                lc.run()                                    # warm-up
+                runs = [lc.run() for _ in range(a.reps)]
+            r = runs[0]
+            row = {"model": name, "property": prop, "states": r.states, "edges": r.edges, "depth": r.depth,
+                   "stay_states": r.stay_states, "live_states": r.live_states, "violated": r.violated,
+                   "kind": r.kind, "trace_len": r.trace_len, "rounds": r.rounds,
+                   "build_ms": min(x.build_ms for x in runs), "trim_ms": min(x.trim_ms for x in runs),
+                   "seconds": min(x.seconds for x in runs),
+                   "build_ms_all": [x.build_ms for x in runs], "trim_ms_all": [x.trim_ms for x in runs],
+                   "seconds_all": [x.seconds for x in runs]}
+            doc["runs"].append(row)
+            print(json.dumps(row), flush=True)
+
+    md = ["| model | property | states / edges / depth | \\|S\\| → \\|L\\| | rounds | build ms | trim ms | run ms |",
+          "|---|---|---|---|---|---|---|---|"]
+    for r in doc["runs"]:
+        md.append(f"| {r['model']} | {r['property']} | {r['states']:,} / {r['edges']:,} / {r['depth']} | "
+                  f"{r['stay_states']:,} → {r['live_states']:,} | {r['rounds']} | {r['build_ms']:.2f} | "
+                  f"{r['trim_ms']:.2f} | {r['seconds'] * 1e3:.2f} |")
+    text = "\n".join(md) + "\n"
+    print(text)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(doc, f, indent=1)
+    if a.md:
+        with open(a.md, "w") as f:
+            f.write(text)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
