@@ -38,8 +38,8 @@
  *                against the same invariants, Asserts and deadlock (the
  *                reference holds no simulation run; semantics below).
  *   kc_live_*    tlc2.TLC's liveness check of the spec's temporal properties
- *                under WF_vars(Next) (the reference holds no liveness output;
- *                semantics below).
+ *                under WF_vars(Next) or per-process weak fairness (the
+ *                reference holds no liveness output; semantics below).
  *   kc_spec_*    host-side access to the lowered spec (canonical tuples) —
  *                used for trace replay and by the parity tests.
  */
@@ -572,8 +572,8 @@ int kc_sim_replay(const kc_model_config *cfg, uint64_t seed, int depth, uint64_t
  * invariants): on this spec 0 and 1 never make the elimination remove a state,
  * and these two do.  0-2 speak of the one client: nc must be 1 (-EINVAL).
  *
- * Weak fairness of Next as a whole only forbids stuttering for ever while a
- * step that changes vars is enabled.  On the finite reachable graph, with the
+ * fairness = 0, WF_vars(Next), the default.  Weak fairness of Next as a whole
+ * only forbids stuttering for ever while a step that changes vars is enabled.  On the finite reachable graph, with the
  * edges s -> s dropped (they are not <Next>_vars steps): s is terminal if it
  * has no successor other than itself, and L is the largest set of reachable
  * stay states in which every state is terminal or has a successor in L.  The
@@ -589,6 +589,30 @@ int kc_sim_replay(const kc_model_config *cfg, uint64_t seed, int depth, uint64_t
  * the walk meets a state it has visited (kind 1, TLC's "Back to state") or a
  * terminal state (kind 2, TLC's "Stuttering").
  *
+ * fairness = 1, per-process weak fairness, PlusCal's `fair process`:
+ *   Spec /\ (\A p \in ProcSet : WF_vars(step of p)).
+ * A model has P = NC + NP + NS <= 5 processes: actor a (clients, then PVC
+ * controllers) is process a, server k is process A + k, A = NC + NP.  In
+ * kc_spec_successors' slot order, slots a and A + a (the actor's API / ListAPI
+ * procedure steps and its own labels, which `fair process` makes fair as
+ * WF(P(self)) /\ WF(API(self)) /\ WF(ListAPI(self)); pc makes the three
+ * mutually exclusive, so one condition per process is equivalent) are steps
+ * of process a, slot 2A + k of process A + k.  Edges s -> s are dropped as
+ * above; enabled(s) is the mask of the processes with a successor other than s,
+ * and s is terminal iff enabled(s) = 0.  Within the reachable stay states S
+ * take the SCCs of the subgraph S induces.  An SCC C of more than one state is
+ * fair iff for every process p some state of C has p disabled or some edge
+ * with both ends in C is a p step.  F = the union of the fair SCCs and the
+ * terminal states of S; L = the states of S from which F is reachable inside
+ * S; the property is violated iff F is not empty.  (For weak fairness the
+ * maximal SCCs suffice: the witnesses of a fair cycle all lie in its SCC, and
+ * an SCC has a cycle through all its states.)  live_states = |L|,
+ * live_terminal = the terminal states in L, kc_live_alive gives L.  The
+ * counterexample is the same shortest prefix to the L state with the smallest
+ * discovery index, a shortest path inside S into F, and then a terminal state
+ * (kind 2) or a cycle inside one fair SCC (kind 1) that for every process p
+ * contains a p step or visits a state with p disabled.
+ *
  * The graph is built by a BFS of the checker's own (the engine is not
  * involved); the invariants are not evaluated.  A state whose Next raises an
  * Assert ends the build: err_kind = 1 and no verdict (kc_engine_* is the tool
@@ -597,6 +621,7 @@ int kc_sim_replay(const kc_model_config *cfg, uint64_t seed, int depth, uint64_t
 typedef struct {
   int property;              /* 0 .. 3, above */
   uint64_t max_states;       /* 0 = 2^24; 16 .. 2^27 */
+  int fairness;              /* 0 WF_vars(Next), 1 per process; else -EINVAL */
 } kc_live_config;
 typedef struct {
   uint64_t states, edges, init; /* the graph: the BFS's distinct, generated - init */
@@ -610,6 +635,12 @@ typedef struct {
   int trace_len, loop_start;    /* states in the counterexample; 0-based index the last
                                    state steps back to, -1 if stuttering */
   double seconds, build_ms, trim_ms; /* host wall time: the run, the graph build, mark and trim */
+  /* fairness = 1 only (0 otherwise): */
+  uint64_t sccs, fair_sccs;     /* SCCs of more than one state in S; the fair ones */
+  uint64_t fair_states;         /* |F| */
+  uint64_t scc_rounds;          /* launches of the SCC, accumulate and closure phases that
+                                   end in a counter read */
+  double scc_ms;                /* host wall time from the end of the trim to L */
 } kc_live_result;
 typedef struct kc_live kc_live;
 /* Model validation and errors as kc_sim_create (-EINVAL, -ENODEV without a
@@ -627,9 +658,19 @@ int64_t kc_live_trace_text(kc_live *l, char *buf, size_t cap);
  * alive bit (1 = in L); for the tests.  Returns the number of states; nothing
  * is written if cap is smaller. */
 int kc_live_alive(kc_live *l, uint64_t *tuples_out, uint8_t *alive_out, uint64_t cap);
+/* Every edge of the last run's graph (a fairness = 1 run; -EINVAL otherwise),
+ * in CSR order: source and target as discovery indices and the process that
+ * takes the step; for the tests.  Returns the number of edges; nothing is
+ * written if cap is smaller. */
+int64_t kc_live_edge_procs(kc_live *l, uint32_t *src_out, uint32_t *dst_out, uint8_t *proc_out, uint64_t cap);
 /* stay(tuple) of a property on the host (no GPU), through the code the kernels
  * run: 1 / 0, < 0 on error. */
 int kc_live_stay(const kc_model_config *cfg, int property, const uint64_t *tuple);
+/* The process (0 .. P-1, above) that takes the step to successor `ordinal` of
+ * the state, in kc_spec_successors order, on the host through the code
+ * k_live_expand runs; -EINVAL if the state has no such successor or its Next
+ * raises an Assert. */
+int kc_live_step_process(const kc_model_config *cfg, const uint64_t *tuple, int ordinal);
 
 /* ----------------------------------------------- Seen-set spill (tests) */
 /* Host self-check of the cold tier's run search (coldset.hip run_find, the

@@ -1,0 +1,196 @@
+"""Liveness checking under per-process weak fairness on the GPU
+(LivenessChecker(fairness="process")) against the independent host model of
+tests/fair_model.py (the oracle's graph, the process of an edge from the two
+tuples, Tarjan on Python sets, F and L by the definition): one test per row of
+the expected-values table — the process of every edge, |S|, the SCC counts,
+|F|, the exact L, the verdict and the validity of the counterexample — then a
+fairness="next" run that still equals the WF_vars(Next) table, the capacity
+and Assert exits, and the command line.
+
+The table's literals were computed with the model on the CPU; every test
+recomputes them with the model and also asserts the literal."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import kubecheck
+from kubecheck import LivenessChecker, ModelConfig, PROPERTIES
+
+import fair_model
+import live_model
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (model, property, |S|, SCCs of more than one state, fair SCCs, |F|, terminal in F, |L|,
+#  |L| under WF_vars(Next), min level of L)
+TABLE = [
+    ("default_101", "ReconcileCompletes", 193, 9, 9, 183, 0, 193, 193, 1),
+    ("default_101", "ClientRestarts", 173, 0, 0, 0, 0, 0, 0, None),
+    ("nodeadlock_110", "ReconcileCompletes", 91, 13, 6, 50, 2, 91, 91, 1),
+    ("nodeadlock_110", "ClientRestarts", 105, 15, 3, 15, 3, 63, 99, 2),
+    ("nodeadlock_110", "SomeActorRestarts", 75, 0, 0, 3, 3, 27, 27, 3),
+    ("nofaults_111", "ReconcileCompletes", 7398, 133, 20, 5370, 0, 7155, 7398, 1),
+    ("nofaults_111", "CleansUpProperly", 427, 31, 3, 15, 0, 427, 427, 25),
+    ("nofaults_111", "ClientRestarts", 7591, 174, 32, 160, 0, 6102, 7591, 2),
+    ("nofaults_111", "SomeActorRestarts", 6545, 0, 0, 0, 0, 0, 0, None),
+]
+
+
+def check_counterexample(m, want, r):
+    """The counterexample is valid (its identity is the device's choice)."""
+    assert r.kind in ("back-to-state", "stuttering")
+    assert r.trace_len == len(r.trace) == len(r.trace_actions) >= r.prefix_len >= 1
+    trace = [tuple(t) for t in r.trace]
+    assert r.trace_actions[0] is None
+    for k in range(1, len(trace)):
+        assert (r.trace_actions[k], trace[k]) in m.successors_of(trace[k - 1]), k
+    fair_model.check_lasso(m, want, [m.index[t] for t in trace], r.prefix_len, r.kind, r.loop_start)
+    assert re.findall(r"^State (\d+):$", r.trace_text, flags=re.M) == [str(k + 1) for k in range(r.trace_len)]
+
+
+@pytest.mark.parametrize("name,pname,n_stay,n_scc,n_fair_scc,n_fair,n_fair_term,n_live,n_live_next,min_level", TABLE,
+                         ids=[f"{t[0]}-{t[1]}" for t in TABLE])
+def test_table_row(oracle, name, pname, n_stay, n_scc, n_fair_scc, n_fair, n_fair_term, n_live, n_live_next,
+                   min_level):
+    m = live_model.model(oracle, name)
+    prop = PROPERTIES.index(pname)
+    want = fair_model.check(m, prop)
+    # the literals against the model
+    assert (len(want.stay), len(want.sccs), len(want.fair_sccs), len(want.fair)) == (n_stay, n_scc, n_fair_scc, n_fair)
+    assert (len(want.fair & want.terminal), len(want.live), want.min_level) == (n_fair_term, n_live, min_level)
+    assert len(m.check(prop).live) == n_live_next and want.live <= m.check(prop).live
+
+    with LivenessChecker(ModelConfig(**live_model.MODELS[name]), pname, fairness="process") as lc:
+        r = lc.run()
+        tuples, alive = lc.alive()
+        src, dst, proc = lc.edge_procs()
+    print(f"{name} {pname}: trim rounds {r.rounds}, SCC rounds {r.scc_rounds}, build {r.build_ms:.2f} ms, "
+          f"trim {r.trim_ms:.2f} ms, scc {r.scc_ms:.2f} ms")
+    assert r.error is None and r.property == pname and r.fairness == "process"
+    assert (r.states, r.edges, r.depth, r.init) == (len(m.states), m.edges, m.depth, m.n_init)
+    # the process of every edge
+    tup = [tuple(int(x) for x in t) for t in tuples]
+    procs = fair_model.procs_of(m)
+    assert len(src) == len(dst) == len(proc) == m.edges
+    got_edges = sorted((m.index[tup[s]], m.index[tup[d]], int(p)) for s, d, p in zip(src, dst, proc))
+    assert got_edges == sorted((i, j, p) for i in range(len(m.states)) for j, p in zip(m.succ[i], procs[i]))
+    # the counters
+    assert (r.stay_states, r.sccs, r.fair_sccs, r.fair_states) == (n_stay, n_scc, n_fair_scc, n_fair)
+    assert (r.live_states, r.live_terminal) == (n_live, want.live_terminal)
+    assert r.violated == want.violated == (n_fair > 0)
+    assert r.scc_rounds >= 1 and r.scc_ms > 0
+    # the exact L
+    got = {(t, bool(a)) for t, a in zip(tup, alive)}
+    assert len(got) == len(tuples) == len(m.states)
+    assert got == {(t, i in want.live) for i, t in enumerate(m.states)}
+    if want.violated:
+        check_counterexample(m, want, r)
+    else:
+        assert (r.kind, r.prefix_len, r.trace_len, r.loop_start, r.trace) == (None, 0, 0, -1, [])
+
+
+def test_fairness_next_is_unchanged(oracle):
+    # the row of tests/test_gpu_liveness.py's table: (140, 479, 15), |S| 105, |L| 99, 3 terminal
+    m = live_model.model(oracle, "nodeadlock_110")
+    want = m.check(PROPERTIES.index("ClientRestarts"))
+    with LivenessChecker(ModelConfig(**live_model.MODELS["nodeadlock_110"]), "ClientRestarts") as lc:
+        d = lc.run()
+    with LivenessChecker(ModelConfig(**live_model.MODELS["nodeadlock_110"]), "ClientRestarts", fairness="next") as lc:
+        r = lc.run()
+        tuples, alive = lc.alive()
+        with pytest.raises(kubecheck.KubecheckError):
+            lc.edge_procs()                      # recorded under fairness="process" only
+    assert r.fairness == d.fairness == "next"
+    assert (r.states, r.edges, r.depth) == (140, 479, 15)
+    assert (r.stay_states, r.live_states, r.live_terminal, r.violated) == (105, 99, 3, True)
+    assert (r.sccs, r.fair_sccs, r.fair_states, r.scc_rounds, r.scc_ms) == (0, 0, 0, 0, 0.0)
+    assert {tuple(int(x) for x in t) for t, a in zip(tuples, alive) if a} == {m.states[i] for i in want.live}
+    # the default is the same run: the counterexample too
+    assert (d.live_states, d.rounds, d.kind, d.prefix_len, d.loop_start, d.trace) == \
+        (r.live_states, r.rounds, r.kind, r.prefix_len, r.loop_start, r.trace)
+    assert r.prefix_len == want.min_level == 2
+
+
+def test_capacity_is_enomem_with_process_fairness(oracle):
+    cfg = ModelConfig(**live_model.MODELS["nofaults_111"])
+    with LivenessChecker(cfg, "CleansUpProperly", max_states=8202, fairness="process") as lc:
+        with pytest.raises(kubecheck.KubecheckError) as e:
+            lc.run()
+        assert e.value.code == -12 and "max_states = 8202" in str(e.value)
+        for call in (lc.alive, lc.edge_procs):
+            with pytest.raises(kubecheck.KubecheckError):
+                call()                           # no completed run
+    # the smallest capacity that holds the graph
+    with LivenessChecker(cfg, "CleansUpProperly", max_states=8203, fairness="process") as lc:
+        r = lc.run()
+    assert (r.states, r.live_states, r.sccs, r.fair_sccs, r.fair_states) == (8203, 427, 31, 3, 15)
+
+
+def test_assert_during_build_gives_no_verdict_with_process_fairness(oracle):
+    m = live_model.Model(oracle, nc=2, np=0, ns=1)
+    assert m.assert_action == "C4"
+    with LivenessChecker(ModelConfig(nc=2, np=0), "SomeActorRestarts", fairness="process") as lc:
+        r = lc.run()
+    assert (r.error, r.error_action) == ("assertion", "C4") and r.error_self in (0, 1)
+    assert (r.violated, r.kind, r.trace_len, r.live_states, r.rounds) == (False, None, 0, 0, 0)
+    assert (r.sccs, r.fair_sccs, r.fair_states, r.scc_rounds, r.scc_ms) == (0, 0, 0, 0, 0.0)
+
+
+def test_cli_fairness_process(oracle):
+    env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "tla-kubernetes_amd"))
+    p = subprocess.run([sys.executable, "-m", "kubecheck.tlc", "-tool", "-fairness", "process", "-config",
+                        os.path.join(ROOT, "models", "Liveness.cfg"), "MC"],
+                       capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 13, p.stderr
+    codes = [int(c) for c in re.findall(r"@!@!@STARTMSG (\d+):\d+ @!@!@", p.stdout)]
+    assert "577736 states generated, 163408 distinct states found, 0 states left on queue." in p.stdout
+    assert "Checking temporal property ReconcileCompletes under weak fairness of every process for" in p.stdout
+    at = codes.index(2192)
+    tail = codes[at:]
+    assert tail[:3] == [2192, 2116, 2264] and codes.count(2116) == 1 and codes.count(2192) == 1
+    assert set(tail[3:-2]) == {2217} and tail[-2] in (2122, 2218) and tail[-1] == 2186
+    n = len(tail) - 5
+    last = re.search(r"STARTMSG (2122|2218):4 @!@!@\n(\d+): (Back to state (\d+)|Stuttering)\n", p.stdout)
+    assert last and int(last.group(2)) == n + 1
+    loop = int(last.group(4)) if last.group(4) else None
+    assert loop is None or 1 <= loop <= n
+    # A valid lasso.  Model_1's graph is too large for the Python model, so the same check is run here and
+    # its counterexample (of the same shape as the printed one: its identity is the device's choice) is
+    # judged state by state: steps of Next, stay from the prefix's end on, and a cycle that has for every
+    # process a step of it or a state with it disabled, which also puts it inside one fair SCC.
+    sp = kubecheck.Spec(ModelConfig())
+    with LivenessChecker(ModelConfig(), "ReconcileCompletes", fairness="process") as lc:
+        r = lc.run()
+    assert r.violated and r.states == 163408 and r.fair_states > 0 and r.fair_sccs >= 1
+    trace = [tuple(t) for t in r.trace]
+    assert trace[0] in {tuple(int(x) for x in t) for t in sp.init()}
+
+    def steps(s):
+        succ, fail = sp.successors(s)
+        assert fail is None
+        return [(a, tuple(int(x) for x in t), sp.step_process(s, k)) for k, (a, t) in enumerate(succ)
+                if tuple(int(x) for x in t) != s]
+
+    for k in range(1, len(trace)):
+        assert (r.trace_actions[k], trace[k]) in [(a, t) for a, t, _ in steps(trace[k - 1])], k
+    assert all(sp.stay("ReconcileCompletes", t) for t in trace[r.prefix_len - 1:])
+    if r.kind == "stuttering":
+        assert not steps(trace[-1])
+    else:
+        assert r.kind == "back-to-state" and r.prefix_len - 1 <= r.loop_start < len(trace)
+        cycle = trace[r.loop_start:]
+        wit = 0
+        for s, t in zip(cycle, cycle[1:] + cycle[:1]):
+            out = steps(s)
+            assert t in [x for _, x, _ in out]
+            enabled = 0
+            for _, x, p in out:
+                enabled |= 1 << p
+                if x == t:
+                    wit |= 1 << p
+            wit |= ~enabled & 7
+        assert wit == 7, bin(wit)                 # Model_1 has 3 processes

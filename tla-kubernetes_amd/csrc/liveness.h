@@ -1,6 +1,7 @@
-// liveness.h — temporal properties under WF_vars(Next): the state predicates
-// the elimination runs on, as KC_HD code shared by the kernels (liveness.hip)
-// and the host (kc_live_stay).  include/kubecheck.h, "Liveness", has the
+// liveness.h — temporal properties under WF_vars(Next) or per-process weak
+// fairness: the state predicates the elimination runs on and the process of a
+// step, as KC_HD code shared by the kernels (liveness.hip) and the host
+// (kc_live_stay, kc_live_step_process).  include/kubecheck.h, "Liveness", has the
 // semantics; DESIGN.md §4.7 the layout.
 //
 // Every property reduces to one question about a predicate `stay`: is there a
@@ -28,6 +29,21 @@ enum LiveProp : int {
 // Properties 0-2 speak of "the" client: they need exactly one.
 KC_HD bool live_prop_ok(int nc, int prop) {
   return prop >= 0 && prop < LP_COUNT && (prop == LP_SomeActorRestarts || nc == 1);
+}
+
+// Fairness conditions (kc_live_config.fairness).
+enum LiveFairness : int {
+  LF_Next = 0,      // WF_vars(Next)
+  LF_Process = 1    // /\_p WF_vars(step of process p): PlusCal's `fair process`
+};
+
+// The process that takes the steps of a slot (kubeapi_spec.h's slot order):
+// actor a is process a (slot a = its API / ListAPI procedure steps, slot A + a
+// = its own labels; pc makes the three mutually exclusive), server k is
+// process A + k.  A model has P = A + NS <= 5 processes.
+template <class M>
+KC_HD int live_slot_process(int slot) {
+  return slot < M::A ? slot : slot < 2 * M::A ? slot - M::A : M::A + (slot - 2 * M::A);
 }
 
 // stay(s) of property `prop`; live_prop_ok(M::NC, prop) must hold.  The

@@ -14,8 +14,9 @@ KubeAPI.toolbox/Model_1, MC.out:2-5):
                           each state checked like the BFS's; the reported walk
                           is replayed on the host (:meth:`Spec.sim_replay`).
 * :class:`LivenessChecker` — tlc2.TLC's liveness check of the spec's temporal
-                          properties under WF_vars(Next): the reachable graph,
-                          the elimination and a lasso counterexample on the GPU.
+                          properties under WF_vars(Next) or per-process weak
+                          fairness (fair SCCs): the reachable graph, the
+                          elimination and a lasso counterexample on the GPU.
 * :mod:`kubecheck.tlc`  — TLC-style command line (``-config MC.cfg MC``) with
                           ``-tool`` message output.
 
@@ -29,13 +30,13 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import (ACTIONS, ERR_KINDS, INVARIANTS, LIVE_KINDS, PROPERTIES, SIM_KINDS, KcLiveConfig,
+from ._lib import (ACTIONS, ERR_KINDS, FAIRNESS, INVARIANTS, LIVE_KINDS, PROPERTIES, SIM_KINDS, KcLiveConfig,
                    KcLiveResult, KcModelConfig, KcResult, KcSimConfig,
                    KcSimResult, KcSqueueConfig, KcSqueueStats, KubecheckError,
                    check, load)
 
 __all__ = ["ModelConfig", "ModelChecker", "CheckResult", "FPSet", "StateQueue", "Spec",
-           "Simulator", "SimResult", "SIM_KINDS", "LivenessChecker", "LiveResult", "PROPERTIES",
+           "Simulator", "SimResult", "SIM_KINDS", "LivenessChecker", "LiveResult", "PROPERTIES", "FAIRNESS",
            "KubecheckError", "ACTIONS", "load", "device_count", "stress_fps_dev", "stress_fp"]
 
 
@@ -375,16 +376,27 @@ class LiveResult:
     trace: List[List[int]] = field(default_factory=list)
     trace_actions: List[Optional[str]] = field(default_factory=list)
     trace_text: str = ""
+    fairness: str = "next"            # a name of FAIRNESS; the fields below are 0 under "next"
+    sccs: int = 0                     # SCCs of more than one state in S
+    fair_sccs: int = 0                # ... that are fair
+    fair_states: int = 0              # |F|
+    scc_rounds: int = 0               # launches of the SCC and closure phases that end in a counter read
+    scc_ms: float = 0.0
 
 
 class LivenessChecker:
-    """A temporal property of KubeAPI.tla under WF_vars(Next) on one GPU
-    (include/kubecheck.h, "Liveness"): the reachable graph, the elimination of
-    the states no fair behaviour can stay in, and a lasso counterexample.
-    `property` is a name of PROPERTIES or its index."""
+    """A temporal property of KubeAPI.tla on one GPU (include/kubecheck.h,
+    "Liveness"): the reachable graph, the elimination of the states no fair
+    behaviour can stay in, and a lasso counterexample.  `property` is a name of
+    PROPERTIES or its index; `fairness` a name of FAIRNESS: "next" is
+    WF_vars(Next), "process" weak fairness of every process (PlusCal's `fair
+    process`), decided on the fair SCCs of the stay states."""
 
     def __init__(self, cfg: Optional[ModelConfig] = None, property="ReconcileCompletes",
-                 max_states: Optional[int] = None, **kw):
+                 max_states: Optional[int] = None, fairness: str = "next", **kw):
+        if fairness not in FAIRNESS:
+            raise ValueError(f"unknown fairness {fairness!r}; known: {FAIRNESS}")
+        self.fairness = fairness
         self.cfg = cfg or ModelConfig(**kw)
         if isinstance(property, str):
             if property not in PROPERTIES:
@@ -394,7 +406,7 @@ class LivenessChecker:
         self._lib = load()
         self._h = C.c_void_p()
         self._c = self.cfg.to_c()
-        self._l = KcLiveConfig(self.property, int(max_states or 0))
+        self._l = KcLiveConfig(self.property, int(max_states or 0), FAIRNESS.index(fairness))
         check("kc_live_create", self._lib.kc_live_create(C.byref(self._c), C.byref(self._l), C.byref(self._h)))
         self.tuple_words = self._lib.kc_spec_tuple_words(self.cfg.nc, self.cfg.np, self.cfg.ns)
 
@@ -408,7 +420,8 @@ class LivenessChecker:
             error_action=ACTIONS[r.err_action] if 0 <= r.err_action < len(ACTIONS) else None,
             error_self=r.err_self, violated=bool(r.violated), kind=LIVE_KINDS.get(r.kind),
             prefix_len=r.prefix_len, trace_len=r.trace_len, loop_start=r.loop_start, seconds=r.seconds,
-            build_ms=r.build_ms, trim_ms=r.trim_ms)
+            build_ms=r.build_ms, trim_ms=r.trim_ms, fairness=self.fairness, sccs=r.sccs, fair_sccs=r.fair_sccs,
+            fair_states=r.fair_states, scc_rounds=r.scc_rounds, scc_ms=r.scc_ms)
         if res.violated:
             n = res.trace_len
             out = np.zeros((n, self.tuple_words), dtype=np.uint64)
@@ -431,6 +444,18 @@ class LivenessChecker:
         check("kc_live_alive", self._lib.kc_live_alive(self._h, _u64(tuples),
                                                        bits.ctypes.data_as(C.POINTER(C.c_uint8)), n))
         return tuples, bits.astype(bool)
+
+    def edge_procs(self):
+        """Every edge of the last run's graph (fairness="process" only): source
+        and target discovery indices and the process that takes the step, as
+        numpy arrays."""
+        n = check("kc_live_edge_procs", self._lib.kc_live_edge_procs(self._h, None, None, None, 0))
+        src, dst = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        proc = np.zeros(n, dtype=np.uint8)
+        u32 = C.POINTER(C.c_uint32)
+        check("kc_live_edge_procs", self._lib.kc_live_edge_procs(
+            self._h, src.ctypes.data_as(u32), dst.ctypes.data_as(u32), proc.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return src, dst, proc
 
     def close(self) -> None:
         if self._h:
@@ -748,6 +773,13 @@ class Spec:
         prop = PROPERTIES.index(property) if isinstance(property, str) else int(property)
         t = np.ascontiguousarray(tup, dtype=np.uint64)
         return bool(check("kc_live_stay", self._lib.kc_live_stay(C.byref(self._c), prop, _u64(t))))
+
+    def step_process(self, tup, ordinal: int) -> int:
+        """The process (actors 0 .. A-1, then the servers) that takes the step
+        to successor `ordinal` of a state, in successors() order, on the host
+        (kc_live_step_process; no GPU)."""
+        t = np.ascontiguousarray(tup, dtype=np.uint64)
+        return check("kc_live_step_process", self._lib.kc_live_step_process(C.byref(self._c), _u64(t), int(ordinal)))
 
     def pack(self, tup) -> np.ndarray:
         t = np.ascontiguousarray(tup, dtype=np.uint64)

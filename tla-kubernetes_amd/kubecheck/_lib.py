@@ -93,8 +93,12 @@ PROPERTIES = ("ReconcileCompletes", "CleansUpProperly", "ClientRestarts", "SomeA
 LIVE_KINDS = {0: None, 1: "back-to-state", 2: "stuttering"}
 
 
+# the fairness condition a liveness check assumes (kc_live_config.fairness = the index)
+FAIRNESS = ("next", "process")
+
+
 class KcLiveConfig(C.Structure):
-    _fields_ = [("property", C.c_int), ("max_states", C.c_uint64)]
+    _fields_ = [("property", C.c_int), ("max_states", C.c_uint64), ("fairness", C.c_int)]
 
 
 class KcLiveResult(C.Structure):
@@ -104,7 +108,9 @@ class KcLiveResult(C.Structure):
                 ("err_kind", C.c_int), ("err_action", C.c_int), ("err_self", C.c_int),
                 ("violated", C.c_int), ("kind", C.c_int), ("prefix_len", C.c_int),
                 ("trace_len", C.c_int), ("loop_start", C.c_int),
-                ("seconds", C.c_double), ("build_ms", C.c_double), ("trim_ms", C.c_double)]
+                ("seconds", C.c_double), ("build_ms", C.c_double), ("trim_ms", C.c_double),
+                ("sccs", C.c_uint64), ("fair_sccs", C.c_uint64), ("fair_states", C.c_uint64),
+                ("scc_rounds", C.c_uint64), ("scc_ms", C.c_double)]
 
 
 class KcSqueueConfig(C.Structure):
@@ -244,6 +250,8 @@ SIGNATURES = [
     ("kc_live_trace_text", C.c_int64, [_P, C.c_char_p, C.c_size_t]),
     ("kc_live_alive", C.c_int, [_P, _U64P, _U8P, C.c_uint64]),
     ("kc_live_stay", C.c_int, [C.POINTER(KcModelConfig), C.c_int, _U64P]),
+    ("kc_live_edge_procs", C.c_int64, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _U8P, C.c_uint64]),
+    ("kc_live_step_process", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_int]),
     ("kc_spec_tuple_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_state_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_init", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_int]),

@@ -2,7 +2,8 @@
 
     python -m kubecheck.tlc [-config MC.cfg] [-deadlock] [-tool] [-nc N -np N -ns N]
                             [-variant V] [-workers N] [-fp K]
-                            [-simulate [num=N]] [-depth D] [-seed S] [-continue] [MC]
+                            [-simulate [num=N]] [-depth D] [-seed S] [-continue]
+                            [-fairness next|process] [MC]
 
 Reads the same inputs as the reference's toolbox run: a TLC model config
 (KubeAPI.toolbox/Model_1/MC.cfg:1-16 — CONSTANT assignments, either direct
@@ -46,7 +47,10 @@ constitutes a counter-example:", the 2217 states, then 2122 "Back to state N"
 or 2218 "Stuttering"; the exit code is 13.  The reference holds no liveness
 output, so these codes and their wording claim no match with TLC's.
 -simulate together with a PROPERTY list is an error.  Without a PROPERTY list
-nothing changes.
+nothing changes.  `-fairness process` checks the properties under weak
+fairness of every process (PlusCal's `fair process`; a .cfg cannot say this,
+so it is an option) instead of WF_vars(Next), the default; the 2192 line names
+the fairness assumed.  It is refused together with -simulate.
 """
 from __future__ import annotations
 
@@ -315,6 +319,15 @@ def sim_messages(r, num_init: int, seed: int, num_walks: int, depth: int, t_star
     return out
 
 
+FAIRNESS_TEXT = {"next": "WF_vars(Next)", "process": "weak fairness of every process"}
+
+
+def live_start_message(name: str, fairness: str, distinct: int, t: float) -> str:
+    """The body of the 2192 line that opens a property's check."""
+    return (f"Checking temporal property {name} under {FAIRNESS_TEXT[fairness]} for the complete state space "
+            f"with {distinct} total distinct states at ({tstamp(t)})")
+
+
 def live_messages(r) -> List[tuple]:
     """-tool messages (code, class, body) for a violated temporal property (a
     kubecheck.LiveResult): 2116, 2264, the 2217 states of the counterexample,
@@ -379,8 +392,13 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("-device", type=int, default=0)
     ap.add_argument("-nocheckfps", action="store_true",
                     help="skip the 'based on the actual fingerprints' estimate (a sort of the seen-set)")
+    ap.add_argument("-fairness", choices=("next", "process"), default=None,
+                    help="temporal properties: WF_vars(Next) (the default) or weak fairness of every process")
     a = ap.parse_args(argv)
     a.simulate, a.num = simulate, (num if num is not None else SIM_DEFAULT_WALKS)
+    if simulate and a.fairness is not None:
+        raise CfgError("-fairness goes with a PROPERTY list; -simulate checks no temporal property")
+    a.fairness = a.fairness or "next"
     if simulate and not 1 <= a.depth <= 65535:
         raise CfgError(f"-depth {a.depth}: expected 1..65535")
     return a
@@ -431,9 +449,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         print(msg(code, body, cls, a.tool), flush=True)
     rc = 0
     for name in props:
-        print(msg(2192, f"Checking temporal property {name} for the complete state space with {r.distinct} "
-                        f"total distinct states at ({tstamp(time.time())})", 0, a.tool), flush=True)
-        with kubecheck.LivenessChecker(mc_cfg, name) as lc:
+        print(msg(2192, live_start_message(name, a.fairness, r.distinct, time.time()), 0, a.tool), flush=True)
+        with kubecheck.LivenessChecker(mc_cfg, name, fairness=a.fairness) as lc:
             lr = lc.run()
         t1 += lr.seconds
         if lr.error is not None or (lr.states, lr.edges) != (r.distinct, r.generated - r.init):
