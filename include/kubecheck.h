@@ -250,6 +250,20 @@ typedef struct {
    * then holds 8-B fingerprint words (16-B {fp, claim} slots otherwise): the
    * same slot count and load in half the HBM, half the per-run clear. */
   int first_claim;
+  /* Symmetry reduction (TLC's SYMMETRY): bit 0 = the
+   * clients are interchangeable, bit 1 = the PVC controllers are; 0 = off.
+   * The seen-set then holds one fingerprint per permutation orbit (the minimum
+   * of the fingerprints of the state's permutations), so distinct, level_width
+   * and act_dist count orbits; generated counts the successors of the states
+   * expanded, one per orbit.  Frontier states, traces and counterexamples stay
+   * real (unpermuted) states.  A bit whose process set has fewer than two
+   * members is ignored; with no bit left the plain engine runs.  Single-GPU
+   * engine only (frontier_hbm_bytes and seen_hbm_bytes included):
+   * kc_engine_create fails with -EINVAL together with variant 5 when the group
+   * moves actor 0 (that Init store names actor 0); kc_shard_create and kc_live_create fail
+   * with -EINVAL (the owner projection is not orbit-invariant; liveness under
+   * symmetry is unsound), and so does kc_sim_create. */
+  int symmetry;
 } kc_model_config;
 
 typedef struct {
@@ -824,6 +838,17 @@ int kc_spec_fingerprint(const kc_model_config *cfg, const uint64_t *tuple, uint6
  * fingerprint (0 expected), <0 on error. */
 int kc_spec_fp_selfcheck(const kc_model_config *cfg, const uint64_t *tuple);
 /* Packed <-> canonical conversion. */
+/* The action of an actor permutation on a state: perm has nc + np entries,
+ * perm[a] = the new index of actor a.  -EINVAL if perm is not a permutation or
+ * maps a client onto a PVC controller. */
+int kc_spec_permute(const kc_model_config *cfg, const uint64_t *tuple, const int *perm, uint64_t *tuple_out);
+/* The fingerprint the engine stores under cfg->symmetry: the minimum of
+ * kc_spec_fingerprint over the orbit (kc_spec_fingerprint itself at 0). */
+int kc_spec_fingerprint_sym(const kc_model_config *cfg, const uint64_t *tuple, uint64_t *fp_out);
+/* Device harness (csrc/sym_selftest.hip): the device code of
+ * kc_spec_fingerprint_sym over n tuples, one lane per state.  -ENODEV without
+ * a GPU. */
+int kc_sym_selftest_fps(const kc_model_config *cfg, const uint64_t *tuples, uint64_t n, uint64_t *fps_out);
 int kc_spec_pack(const kc_model_config *cfg, const uint64_t *tuple, uint64_t *packed_out);
 int kc_spec_unpack(const kc_model_config *cfg, const uint64_t *packed, uint64_t *tuple_out);
 

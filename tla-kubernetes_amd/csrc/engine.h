@@ -61,6 +61,9 @@ class EngineBase {
 };
 
 std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg);
+// the engine under symmetry reduction (engine_sym.hip); eff = a mask with a
+// non-trivial group (kubeapi_spec.h sym_effective); nullptr for other models
+std::unique_ptr<EngineBase> make_engine_sym(const kc_model_config& cfg, int eff);
 const char* action_name(int a);
 // TLA+-style rendering of a canonical tuple (spec_abi.cpp)
 std::string format_tuple(const uint64_t* tuple, int nc, int np, int ns, bool ghost = false);

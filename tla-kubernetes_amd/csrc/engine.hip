@@ -30,8 +30,14 @@
 #include "kc_common.h"
 #include "squeue.h"
 
+// The symmetric instantiations (EngineT<SymModel<..>>, kc_model_config.symmetry)
+// are compiled from this same text as a second translation unit
+// (engine_sym.hip defines KC_ENGINE_SYM_TU and includes this file): there the
+// launch helpers below are that unit's own copies, and it defines
+// make_engine_sym instead of make_engine and the C-ABI.
 namespace kc {
 
+#ifndef KC_ENGINE_SYM_TU
 namespace {
 
 const char* kActionNames[A_COUNT] = {
@@ -40,6 +46,9 @@ const char* kActionNames[A_COUNT] = {
     "PVCHavePVCs", "PVCDone", "APIStart"};
 
 }  // namespace
+#else
+namespace {
+#endif
 
 // chunk_base += the chunk's new states (last exclusive offset + last count,
 // or the tile scan's total tile_off[tiles]); cand_total = sum of the
@@ -113,7 +122,9 @@ __global__ void k_level_reset(Counters* __restrict__ C) {
   }
 }
 
+#ifndef KC_ENGINE_SYM_TU
 const char* action_name(int a) { return (a >= 0 && a < A_COUNT) ? kActionNames[a] : "?"; }
+#endif
 
 // Deferred-frontier redo from level X: every fingerprint claimed at a
 // successor level above X (inserted by level X or later) leaves the
@@ -158,6 +169,10 @@ __global__ void k_adjacent_min_gap(const unsigned long long* __restrict__ s, uin
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i + 1 < n) atomicMin(out, s[i + 1] - s[i]);
 }
+
+#ifdef KC_ENGINE_SYM_TU
+}  // namespace
+#endif
 
 constexpr uint64_t kMaxChunk = (1ull << 27) - 256;
 
@@ -288,15 +303,22 @@ class EngineT final : public EngineBase {
     const auto t0 = std::chrono::steady_clock::now();
 
     // ---- Init (KubeAPI.tla:455-469), on the host: 2^NC states
-    const int ni = M::num_init();
-    std::vector<State> init(ni);
-    std::vector<uint64_t> fps(ni);
+    // (under symmetry the fingerprint is the orbit's: of the Init states of
+    // one orbit the first is kept, the others count as generated only)
+    const int ni_all = M::num_init();
+    std::vector<State> init;
+    std::vector<uint64_t> fps;
     uint64_t cand = 0;
-    for (int k = 0; k < ni; ++k) {
-      M::init_state(k, init[k], cfg_.variant);
-      fps[k] = M::fingerprint(init[k]);
-      cand += (uint64_t)M::plan(init[k], flags_).total;
+    for (int k = 0; k < ni_all; ++k) {
+      State s0;
+      M::init_state(k, s0, cfg_.variant);
+      const uint64_t fp0 = M::fingerprint(s0);
+      if (std::find(fps.begin(), fps.end(), fp0) != fps.end()) continue;
+      init.push_back(s0);
+      fps.push_back(fp0);
+      cand += (uint64_t)M::plan(s0, flags_).total;
     }
+    const int ni = (int)init.size();
     // the seen-set allocation is kept across runs (cleared each run), like a
     // TLC FPSet pre-sized with -fpmem; it grows by rehash when needed
     const uint64_t fp_slots = cfg_.fpset_slots ? cfg_.fpset_slots : (1ull << 20);
@@ -343,8 +365,8 @@ class EngineT final : public EngineBase {
     KC_HIP_TRY(hipMemsetAsync(d_ctr_, 0, sizeof(Counters), st_));
     if (d_ovf_cnt_) KC_HIP_TRY(hipMemsetAsync(d_ovf_cnt_, 0, 8, st_));
     if (defer_now_) KC_TRY(counter_snap(0));
-    res->init = ni;
-    res->generated = ni;
+    res->init = ni_all;
+    res->generated = ni_all;
     res->distinct = ni;
     init_states_ = init;
 
@@ -1914,7 +1936,21 @@ size_t EngineT<M>::trace_text(char* buf, size_t cap) const {
   return s.size() + 1;
 }
 
+#ifdef KC_ENGINE_SYM_TU
+// eff = sym_effective(cfg): a mask with a non-trivial group
+std::unique_ptr<EngineBase> make_engine_sym(const kc_model_config& cfg, int eff) {
+#define KC_MAKE(a, b, c, m)                                           \
+  if (cfg.nc == a && cfg.np == b && cfg.ns == c && eff == m)          \
+    return std::unique_ptr<EngineBase>(new EngineT<SymModel<a, b, c, m>>(cfg));
+  KC_FOR_EACH_SYM_MODEL(KC_MAKE)
+#undef KC_MAKE
+  return nullptr;
+}
+#else
 std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg) {
+  // symmetry with a non-trivial group: the SymModel instantiations
+  // (engine_sym.hip); a mask that selects no group runs the plain engine
+  if (const int eff = sym_effective(cfg.nc, cfg.np, cfg.symmetry)) return make_engine_sym(cfg, eff);
 #define KC_MAKE(a, b, c)                                              \
   if (cfg.nc == a && cfg.np == b && cfg.ns == c)                      \
     return std::unique_ptr<EngineBase>(new EngineT<Model<a, b, c>>(cfg));
@@ -1922,8 +1958,11 @@ std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg) {
 #undef KC_MAKE
   return nullptr;
 }
+#endif
 
 }  // namespace kc
+
+#ifndef KC_ENGINE_SYM_TU
 
 using namespace kc;
 
@@ -1946,6 +1985,18 @@ void kc_model_config_default(kc_model_config* c) {
 int kc_engine_create(const kc_model_config* cfg, kc_engine** out) {
   if (!cfg || !out) { set_error("kc_engine_create: NULL argument"); return -EINVAL; }
   *out = nullptr;
+  if (cfg->symmetry & ~3) {
+    set_error("kc_engine_create: symmetry %d outside 0..3 (bit 0 clients, bit 1 PVC controllers)", cfg->symmetry);
+    return -EINVAL;
+  }
+  if (const int eff = sym_effective(cfg->nc, cfg->np, cfg->symmetry)) {
+    // variant 5's Init store names actor 0 in a version vector: not closed
+    // under a group that moves actor 0
+    if (cfg->variant == 5 && ((eff & 1) || cfg->nc == 0)) {
+      set_error("kc_engine_create: variant 5 is not symmetric under symmetry=%d (its Init store names actor 0)", cfg->symmetry);
+      return -EINVAL;
+    }
+  }
   auto impl = make_engine(*cfg);
   if (!impl) {
     set_error("kc_engine_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);
@@ -2001,3 +2052,4 @@ int kc_engine_kernel_times(kc_engine* e, double* ms4, uint64_t* launches4) {
 }
 
 }  // extern "C"
+#endif  // KC_ENGINE_SYM_TU

@@ -886,6 +886,154 @@ struct Model {
     return (uint32_t)owner_hash(x.w[0], wo);
   }
 
+  // ------------------------------------------------------------ symmetry
+  // TLC's SYMMETRY: the clients are interchangeable among
+  // themselves and so are the PVC controllers.  A permutation pi of the
+  // actors (clients onto clients, controllers onto controllers) acts on a
+  // state by moving every per-actor value to its new actor and renaming the
+  // actors inside every version vector.  Every pi is a product of
+  // transpositions, and swap_actors<i, j> is the transposition's whole action
+  // on the packed form:
+  //   * actor words i and j trade places, and so do their objs masks;
+  //   * vv bits i and j trade places in u of every full objcode;
+  //   * every U-mask is bit-permuted by the induced map of u (vv bits i and j
+  //     of the INDEX exchanged): one masked delta-swap per word, since the
+  //     masks of an objs word sit at multiples of U (bit 63 of word 0, the
+  //     lostUpdate ghost, is outside the swap's mask and stays).
+  template <int i, int j>
+  static constexpr uint64_t dswap_mask() {          // per U-mask: index bit i set, bit j clear
+    uint64_t r = 0;
+    for (int u = 0; u < U; ++u)
+      if (((u >> i) & 1) && !((u >> j) & 1)) r |= 1ull << u;
+    return r;
+  }
+  template <int i, int j>
+  static constexpr uint64_t dswap_mask_packed() {   // the same at every mask of an objs word
+    uint64_t r = 0;
+    for (int k = 0; k < OBJ_PER_WORD; ++k) r |= dswap_mask<i, j>() << ((k * U) & 63);
+    return r;
+  }
+  template <int i, int j>
+  KC_HD static uint64_t dswap(uint64_t m, uint64_t mask) {
+    constexpr int sh = (1 << j) - (1 << i);
+    const uint64_t t = (m ^ (m >> sh)) & mask;
+    return m ^ t ^ (t << sh);
+  }
+  template <int i, int j>
+  KC_HD static uint64_t swap_vv_oc(uint64_t w, int off) {   // one objcode field of an actor word
+    const int oc = g(w, off, OBJB);
+    const int u = oc - 3;
+    const int d = ((u >> i) ^ (u >> j)) & 1;
+    return oc >= 3 ? sw(w, off, OBJB, 3 + (u ^ (d << i) ^ (d << j))) : w;
+  }
+  template <int i, int j>
+  KC_HD static void swap_actors(State& s) {
+    static_assert(i < j && j < A && is_client(i) == is_client(j), "a transposition within one process set");
+    s.w[0] = dswap<i, j>(s.w[0], dswap_mask<i, j>());
+    static_for<A>([&](auto AI) {
+      constexpr int a = AI;
+      uint64_t w = s.w[1 + a];
+      w = swap_vv_oc<i, j>(w, F_OBJ);
+      w = swap_vv_oc<i, j>(w, F_SOBJ);
+      w = swap_vv_oc<i, j>(w, F_RQOBJ);
+      s.w[1 + a] = w;
+    });
+    static_for<OBJ_WORDS>([&](auto KI) {
+      constexpr int k = KI;
+      s.w[1 + A + k] = dswap<i, j>(s.w[1 + A + k], dswap_mask_packed<i, j>());
+    });
+    const uint64_t wi = s.w[1 + i], oi = objs<i>(s), oj = objs<j>(s);
+    s.w[1 + i] = s.w[1 + j];
+    s.w[1 + j] = wi;
+    set_objs<i>(s, oj);
+    set_objs<j>(s, oi);
+  }
+  // Visit g.y for every g != identity of Sym({b .. b+k-1}), k <= 3, one
+  // adjacent transposition per step (y is left at the last element visited;
+  // the walk s1, s2, s1, s2, s1 from any start meets all of S3).
+  static constexpr int fact(int k) { return k <= 1 ? 1 : k * fact(k - 1); }
+  template <int b, int k, class F>
+  KC_HD static void walk_set(State& y, F&& visit) {
+    static_assert(k <= 3, "symmetry: at most 3 interchangeable processes of a kind");
+    static_for<fact(k) - 1>([&](auto TI) {
+      constexpr int t = TI;
+      swap_actors<b + (t & 1), b + (t & 1) + 1>(y);
+      visit(y);
+    });
+  }
+  // The symmetry group of MASK (bit 0: clients, bit 1: PVC controllers)
+  template <int MASK>
+  static constexpr int sym_kc() { return (MASK & 1) && NC >= 2 ? NC : 1; }
+  template <int MASK>
+  static constexpr int sym_kp() { return (MASK & 2) && NP >= 2 ? NP : 1; }
+  template <int MASK>
+  static constexpr int sym_order() { return fact(sym_kc<MASK>()) * fact(sym_kp<MASK>()); }
+  // min of fingerprint<0>(g.x) over the non-identity g of the group (~0 for
+  // the trivial group): fp_sym without the identity's term, which callers
+  // with the parent's fold at hand take from fingerprint_succ.  The minimum
+  // of the 63-bit folds over an orbit is the same for every state of the
+  // orbit, with no state comparison.
+  template <int MASK>
+  KC_HD static uint64_t fp_sym_rest(const State& x) {
+    uint64_t m = ~0ull;
+    if constexpr (sym_order<MASK>() > 1) {
+      State y = x;
+      auto visit = [&](const State& z) {
+        const uint64_t f = fingerprint<0>(z);
+        m = f < m ? f : m;
+      };
+      constexpr int kc_ = sym_kc<MASK>(), kp_ = sym_kp<MASK>();
+      walk_set<NC, kp_>(y, visit);
+      static_for<fact(kc_) - 1>([&](auto TI) {
+        constexpr int t = TI;
+        swap_actors<(t & 1), (t & 1) + 1>(y);
+        visit(y);
+        walk_set<NC, kp_>(y, visit);
+      });
+    }
+    return m;
+  }
+  template <int MASK>
+  KC_HD static uint64_t fp_sym(const State& x) {
+    const uint64_t a = fingerprint<0>(x), b = fp_sym_rest<MASK>(x);
+    return a < b ? a : b;
+  }
+  // Host: fp_sym for a runtime mask (kc_model_config.symmetry)
+  static uint64_t fp_sym_rt(const State& x, int mask) {
+    const int m = ((mask & 1) && NC >= 2 ? 1 : 0) | ((mask & 2) && NP >= 2 ? 2 : 0);
+    return m == 3 ? fp_sym<3>(x) : m == 2 ? fp_sym<2>(x) : m == 1 ? fp_sym<1>(x) : fingerprint<0>(x);
+  }
+  // Host: the action of a runtime permutation (perm[a] = new index of actor
+  // a), as transpositions.  False if perm is no permutation of the actors or
+  // moves a client onto a controller.
+  static void swap_actors_rt(State& s, int i, int j) {
+    static_for<A>([&](auto II) {
+      static_for<A>([&](auto JI) {
+        constexpr int ci = decltype(II)::value, cj = decltype(JI)::value;
+        if constexpr (ci < cj && is_client(ci) == is_client(cj))
+          if (i == ci && j == cj) swap_actors<ci, cj>(s);
+      });
+    });
+  }
+  static bool permute(const State& s, const int* perm, State& out) {
+    int p[A];
+    unsigned seen = 0;
+    for (int a = 0; a < A; ++a) {
+      p[a] = perm[a];
+      if (p[a] < 0 || p[a] >= A || is_client(p[a]) != is_client(a) || ((seen >> p[a]) & 1)) return false;
+      seen |= 1u << p[a];
+    }
+    out = s;
+    for (int a = 0; a < A; ++a)
+      while (p[a] != a) {           // (a b) first, then what is left: rho = pi . (a b)
+        const int b = p[a];
+        swap_actors_rt(out, a < b ? a : b, a < b ? b : a);
+        p[a] = p[b];
+        p[b] = b;
+      }
+    return true;
+  }
+
   // ------------------------------------------------ canonical tuple (ABI)
   // Interchange form shared with tests (include/kubecheck.h): word 0 =
   // apiState as a U mask; then 19 words per process: pc, op, obj, kind, sr,
@@ -954,5 +1102,39 @@ struct Model {
 #define KC_FOR_EACH_MODEL(X) \
   X(1, 1, 1) X(2, 1, 1) X(1, 2, 1) X(2, 0, 1) X(1, 1, 2) X(1, 3, 1) X(2, 2, 1) X(1, 0, 1) X(0, 1, 1) \
   X(1, 1, 0)
+
+// The model under symmetry reduction (kc_model_config.symmetry = MASK): the
+// same states, actions and invariants; only the fingerprint is the orbit's
+// (fp_sym).  The engine's kernels take every fingerprint from M::, so
+// EngineT<SymModel<..>> is the unchanged kernel text instantiated once more.
+// The identity's term keeps the incremental fold of the parent.  OWN is
+// accepted for the kernels' sake and ignored: the owner projection is not
+// orbit-invariant, and the sharded entry points refuse symmetry.
+template <int NC_, int NP_, int NS_, int MASK_>
+struct SymModel : Model<NC_, NP_, NS_> {
+  using Base = Model<NC_, NP_, NS_>;
+  using State = typename Base::State;
+  static constexpr int MASK = MASK_;
+  static_assert(Base::template sym_order<MASK_>() > 1, "SymModel: trivial group");
+  template <int OWN = 0>
+  KC_HD static uint64_t fingerprint(const State& s) {
+    return Base::template fp_sym<MASK_>(s);
+  }
+  template <int OWN = 0>
+  KC_HD static uint64_t fingerprint_succ(const State& s, uint64_t fold_s, const State& x, int who,
+                                         uint32_t proj_s = 0) {
+    const uint64_t a = Base::template fingerprint_succ<0>(s, fold_s, x, who, proj_s);
+    const uint64_t b = Base::template fp_sym_rest<MASK_>(x);
+    return a < b ? a : b;
+  }
+};
+// Models with a non-trivial group and the masks that select one:
+// X(NC, NP, NS, MASK)
+#define KC_FOR_EACH_SYM_MODEL(X) \
+  X(2, 1, 1, 1) X(1, 2, 1, 2) X(2, 0, 1, 1) X(1, 3, 1, 2) X(2, 2, 1, 1) X(2, 2, 1, 2) X(2, 2, 1, 3)
+// cfg.symmetry restricted to the process sets that have two members or more
+inline int sym_effective(int nc, int np, int symmetry) {
+  return ((symmetry & 1) && nc >= 2 ? 1 : 0) | ((symmetry & 2) && np >= 2 ? 2 : 0);
+}
 
 }  // namespace kc

@@ -1078,6 +1078,10 @@ extern "C" {
 int kc_live_create(const kc_model_config* cfg, const kc_live_config* live, kc_live** out) {
   if (!cfg || !live || !out) { set_error("kc_live_create: NULL argument"); return -EINVAL; }
   *out = nullptr;
+  if (cfg->symmetry) {
+    set_error("kc_live_create: symmetry is not supported (liveness checking under symmetry reduction is unsound)");
+    return -EINVAL;
+  }
   auto impl = make_live(*cfg);
   if (!impl) {
     set_error("kc_live_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);

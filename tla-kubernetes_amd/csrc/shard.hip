@@ -2344,6 +2344,11 @@ extern "C" {
 int kc_shard_create(const kc_model_config* cfg, int rank, int world, kc_shard** out) {
   if (!cfg || !out) { set_error("kc_shard_create: NULL"); return -EINVAL; }
   *out = nullptr;
+  if (cfg->symmetry) {
+    set_error("kc_shard_create: symmetry is not supported in the sharded loop (the owner projection is not "
+              "orbit-invariant)");
+    return -EINVAL;
+  }
   auto impl = make_shard(*cfg, rank, world);
   if (!impl) {
     set_error("kc_shard_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);

@@ -400,6 +400,10 @@ extern "C" {
 int kc_sim_create(const kc_model_config* cfg, const kc_sim_config* sim, kc_sim** out) {
   if (!cfg || !sim || !out) { set_error("kc_sim_create: NULL argument"); return -EINVAL; }
   *out = nullptr;
+  if (cfg->symmetry) {
+    set_error("kc_sim_create: symmetry is not supported (random walks keep no seen-set to reduce)");
+    return -EINVAL;
+  }
   if (sim->num_walks < 1 || sim->num_walks > KC_SIM_MAX_WALKS) {
     set_error("kc_sim_create: num_walks %llu outside 1..2^30", (unsigned long long)sim->num_walks);
     return -EINVAL;

@@ -242,6 +242,34 @@ int kc_spec_fingerprint(const kc_model_config* cfg, const uint64_t* tuple, uint6
   });
 }
 
+int kc_spec_permute(const kc_model_config* cfg, const uint64_t* tuple, const int* perm, uint64_t* out) {
+  if (!cfg || !tuple || !perm || !out) { set_error("kc_spec_permute: NULL"); return -EINVAL; }
+  return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {
+    using M = decltype(m);
+    typename M::State s, t;
+    if (!M::from_tuple(tuple, s)) { set_error("kc_spec_permute: bad tuple"); return -EINVAL; }
+    if (!M::permute(s, perm, t)) {
+      set_error("kc_spec_permute: perm is not a permutation of the clients among themselves and the "
+                "PVC controllers among themselves");
+      return -EINVAL;
+    }
+    M::to_tuple(t, out);
+    return 0;
+  });
+}
+
+int kc_spec_fingerprint_sym(const kc_model_config* cfg, const uint64_t* tuple, uint64_t* fp) {
+  if (!cfg || !tuple || !fp) { set_error("kc_spec_fingerprint_sym: NULL"); return -EINVAL; }
+  if (cfg->symmetry & ~3) { set_error("kc_spec_fingerprint_sym: symmetry %d outside 0..3", cfg->symmetry); return -EINVAL; }
+  return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {
+    using M = decltype(m);
+    typename M::State s;
+    if (!M::from_tuple(tuple, s)) { set_error("kc_spec_fingerprint_sym: bad tuple"); return -EINVAL; }
+    *fp = M::fp_sym_rt(s, cfg->symmetry);
+    return 0;
+  });
+}
+
 int kc_spec_fp_selfcheck(const kc_model_config* cfg, const uint64_t* tuple) {
   if (!cfg || !tuple) { set_error("kc_spec_fp_selfcheck: NULL"); return -EINVAL; }
   return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {

@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Union
 
 import numpy as np
 
@@ -42,6 +42,10 @@ __all__ = ["ModelConfig", "ModelChecker", "CheckResult", "FPSet", "StateQueue", 
 
 def device_count() -> int:
     return load().kc_device_count()
+
+
+# ModelConfig.symmetry by name -> kc_model_config.symmetry
+SYMMETRY_SETS = {"clients": 1, "controllers": 2, "actors": 3}
 
 
 @dataclass
@@ -84,11 +88,32 @@ class ModelConfig:
     # levels and every counted level of the sharded loop (not with tlc_order
     # or the seen-set spill there); CheckResult.claim_mode says what ran
     first_claim: bool = False
+    # symmetry reduction (TLC's SYMMETRY): 0 (off), "clients", "controllers" or
+    # "actors" (both), or the mask itself (bit 0 clients, bit 1 controllers).
+    # The seen-set keeps one fingerprint per permutation orbit, so distinct,
+    # level_width and act_dist count orbits; frontier states and traces stay
+    # real states.  The single-GPU engine only (include/kubecheck.h).
+    symmetry: Union[int, str] = 0
+
+    @property
+    def symmetry_mask(self) -> int:
+        s = self.symmetry
+        if isinstance(s, str):
+            if s not in SYMMETRY_SETS:
+                raise ValueError(f"symmetry {s!r}: expected 0, " + ", ".join(repr(k) for k in SYMMETRY_SETS))
+            return SYMMETRY_SETS[s]
+        s = int(s or 0)
+        if s & ~3:
+            raise ValueError(f"symmetry {s}: the mask is 0..3 (bit 0 clients, bit 1 controllers)")
+        return s
 
     def to_c(self) -> KcModelConfig:
         c = KcModelConfig()
         for f in KcModelConfig._fields_:
             if f[0] == "spill_dir":
+                continue
+            if f[0] == "symmetry":
+                c.symmetry = self.symmetry_mask
                 continue
             setattr(c, f[0], int(getattr(self, f[0])))
         # the C string must outlive the engine's use of the config (copied at create)
@@ -737,6 +762,33 @@ class Spec:
         fp = C.c_uint64()
         check("kc_spec_fingerprint", self._lib.kc_spec_fingerprint(C.byref(self._c), _u64(t), C.byref(fp)))
         return fp.value
+
+    def fingerprint_sym(self, tup) -> int:
+        """The fingerprint the engine stores under cfg.symmetry: the minimum
+        of fingerprint() over the state's permutation orbit."""
+        t = np.ascontiguousarray(tup, dtype=np.uint64)
+        fp = C.c_uint64()
+        check("kc_spec_fingerprint_sym", self._lib.kc_spec_fingerprint_sym(C.byref(self._c), _u64(t), C.byref(fp)))
+        return fp.value
+
+    def permute(self, tup, perm) -> np.ndarray:
+        """The state with actor a moved to index perm[a] (clients among
+        themselves, controllers among themselves)."""
+        t = np.ascontiguousarray(tup, dtype=np.uint64)
+        if len(perm) != self.cfg.nc + self.cfg.np:
+            raise ValueError(f"perm has {len(perm)} entries, the model {self.cfg.nc + self.cfg.np} actors")
+        p = (C.c_int * len(perm))(*[int(x) for x in perm])
+        out = np.zeros(self.tuple_words, dtype=np.uint64)
+        check("kc_spec_permute", self._lib.kc_spec_permute(C.byref(self._c), _u64(t), p, _u64(out)))
+        return out
+
+    def sym_selftest_fps(self, tuples) -> np.ndarray:
+        """fingerprint_sym of every row of `tuples`, computed on the GPU by
+        the device code the engine's kernels call (test harness)."""
+        t = np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, self.tuple_words)
+        out = np.zeros(len(t), dtype=np.uint64)
+        check("kc_sym_selftest_fps", self._lib.kc_sym_selftest_fps(C.byref(self._c), _u64(t), len(t), _u64(out)))
+        return out
 
     def fp_selfcheck(self, tup) -> int:
         """Successors whose incremental (kernel) fingerprint differs from the

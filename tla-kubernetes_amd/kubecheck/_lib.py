@@ -38,6 +38,7 @@ class KcModelConfig(C.Structure):
         ("seen_hbm_bytes", C.c_uint64), ("seen_host_bytes", C.c_uint64),
         ("tlc_order", C.c_int),
         ("first_claim", C.c_int),
+        ("symmetry", C.c_int),
     ]
 
 
@@ -259,6 +260,9 @@ SIGNATURES = [
     ("kc_spec_check", C.c_int, [C.POINTER(KcModelConfig), _U64P]),
     ("kc_spec_fingerprint", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
     ("kc_spec_fp_selfcheck", C.c_int, [C.POINTER(KcModelConfig), _U64P]),
+    ("kc_spec_permute", C.c_int, [C.POINTER(KcModelConfig), _U64P, _IP, _U64P]),
+    ("kc_spec_fingerprint_sym", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
+    ("kc_sym_selftest_fps", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P]),
     ("kc_spec_pack", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
     ("kc_spec_unpack", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
 ]

@@ -47,7 +47,19 @@ constitutes a counter-example:", the 2217 states, then 2122 "Back to state N"
 or 2218 "Stuttering"; the exit code is 13.  The reference holds no liveness
 output, so these codes and their wording claim no match with TLC's.
 -simulate together with a PROPERTY list is an error.  Without a PROPERTY list
-nothing changes.  `-fairness process` checks the properties under weak
+nothing changes.
+
+Symmetry: `SYMMETRY name` in the cfg (models/Symmetry.cfg) turns on symmetry
+reduction, TLC's way: the seen-set keeps one fingerprint per permutation
+orbit, the states explored and every trace stay real states.  There is no
+TLA+ front end, so no Permutations(...) expression: the name is one of the
+build-defined sets SymClients, SymControllers (use with -np 2 or more) and
+SymActors (both).  The 2187 banner then names the set, and the distinct
+counts are orbit counts.  SYMMETRY together with a PROPERTY list or with
+-simulate is an error (liveness under symmetry is unsound, as TLC warns; a
+random walk has no seen-set to reduce).  Without the keyword nothing changes.
+
+`-fairness process` checks the properties under weak
 fairness of every process (PlusCal's `fair process`; a .cfg cannot say this,
 so it is an option) instead of WF_vars(Next), the default; the 2192 line names
 the fairness assumed.  It is refused together with -simulate.
@@ -66,6 +78,9 @@ KNOWN_INVARIANTS = ("TypeOK", "OnlyOneVersion")          # KubeAPI.tla:776,787
 # writer has not read (the optimistic concurrency HasRead gives Update,
 # :733), with its lostUpdate history variable; run with -variant 1 it fails
 BUILD_INVARIANTS = ("NoLostUpdate",)
+# build-defined symmetry sets (there is no Permutations(...) to evaluate):
+# the cfg's SYMMETRY name -> ModelConfig.symmetry
+SYMMETRY_NAMES = {"SymClients": "clients", "SymControllers": "controllers", "SymActors": "actors"}
 KNOWN_CONSTANTS = ("REQUESTS_CAN_FAIL", "REQUESTS_CAN_TIMEOUT", "defaultInitValue")  # :4-6,374
 
 
@@ -90,10 +105,11 @@ def parse_cfg(cfg_text: str, defs: Optional[Dict[str, str]] = None) -> dict:
     """Parse a TLC .cfg (the subset MC.cfg uses)."""
     defs = defs or {}
     toks = _strip_comments(cfg_text).split()
-    out: dict = {"constants": {}, "specification": None, "invariants": [], "properties": []}
+    out: dict = {"constants": {}, "specification": None, "invariants": [], "properties": [],
+                 "symmetry": None}
     i, section = 0, None
     keywords = {"CONSTANT", "CONSTANTS", "SPECIFICATION", "INVARIANT", "INVARIANTS",
-                "PROPERTY", "PROPERTIES", "INIT", "NEXT"}
+                "PROPERTY", "PROPERTIES", "INIT", "NEXT", "SYMMETRY"}
     while i < len(toks):
         t = toks[i]
         if t in keywords:
@@ -117,6 +133,13 @@ def parse_cfg(cfg_text: str, defs: Optional[Dict[str, str]] = None) -> dict:
             out["invariants"].append(t)
         elif section in ("PROPERTY", "PROPERTIES"):
             out["properties"].append(t)
+        elif section == "SYMMETRY":
+            if out["symmetry"] is not None:
+                raise CfgError(f"SYMMETRY takes one name, got {out['symmetry']!r} and {t!r}")
+            if t not in SYMMETRY_NAMES:
+                raise CfgError(f"SYMMETRY {t}: expected one of {tuple(SYMMETRY_NAMES)} (build-defined; "
+                               "Permutations(...) expressions are not evaluated)")
+            out["symmetry"] = t
         else:
             raise CfgError(f"unsupported cfg token {t!r}")
         i += 1
@@ -146,6 +169,8 @@ def model_from_cfg(cfg: dict) -> dict:
     kw["invariants"] = (1 if "TypeOK" in cfg["invariants"] else 0) | \
         (2 if "OnlyOneVersion" in cfg["invariants"] else 0) | \
         (4 if "NoLostUpdate" in cfg["invariants"] else 0)
+    if cfg.get("symmetry"):
+        kw["symmetry"] = SYMMETRY_NAMES[cfg["symmetry"]]
     return kw
 
 
@@ -161,6 +186,11 @@ def check_from_cfg(cfg: dict, simulate: bool = False):
         raise CfgError(f"unknown temporal property(ies) {bad}; known: {PROPERTIES}")
     if props and simulate:
         raise CfgError("-simulate checks no temporal PROPERTY (liveness needs the whole state graph)")
+    if cfg.get("symmetry") and props:
+        raise CfgError(f"SYMMETRY {cfg['symmetry']} with a PROPERTY list: liveness checking under symmetry "
+                       "reduction is unsound")
+    if cfg.get("symmetry") and simulate:
+        raise CfgError(f"SYMMETRY {cfg['symmetry']} with -simulate: a random walk has no seen-set to reduce")
     return model_from_cfg(dict(cfg, properties=[])), props
 
 
@@ -222,7 +252,7 @@ def tstamp(t: float) -> str:
 
 
 def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = None,
-             engine: str = "", ngpus: int = 1) -> List[tuple]:
+             engine: str = "", ngpus: int = 1, symmetry: Optional[str] = None) -> List[tuple]:
     """TLC -tool messages (code, class, body) for one check's result, in the
     order of the reference run (MC.out:1-1108).  SANY's (2220/2219) and the
     expression-level coverage (2221) are not produced: there is no TLA+ front
@@ -231,7 +261,8 @@ def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = 
     add = lambda code, text, cls=0: out.append((code, cls, text))  # noqa: E731
     add(2262, f"kubecheck (TLC-compatible counts) {engine}".rstrip())
     add(2187, f"Running breadth-first search Model-Checking with {ngpus} MI355X GPU(s) "
-              f"(kubecheck ClaimSet FPSet, HBM StateQueue).")
+              f"(kubecheck ClaimSet FPSet, HBM StateQueue)."
+              + (f" Symmetry set: {symmetry}." if symmetry else ""))
     add(2185, f"Starting... ({tstamp(t_start)})")
     add(2189, "Computing initial states...")
     add(2190, f"Finished computing initial states: {r.init} distinct states generated at {tstamp(t_start)}.")
@@ -417,7 +448,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 1
     tla_path = os.path.join(os.path.dirname(os.path.abspath(cfg_path)), f"{a.spec}.tla")
     defs = parse_defs(open(tla_path).read()) if os.path.exists(tla_path) else {}
-    kw, props = check_from_cfg(parse_cfg(open(cfg_path).read(), defs), a.simulate)
+    parsed = parse_cfg(open(cfg_path).read(), defs)
+    kw, props = check_from_cfg(parsed, a.simulate)
 
     import kubecheck
 
@@ -439,7 +471,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         r = mc.run()
         prob = None if (a.nocheckfps or r.error is not None) else mc.check_fps()[1]
     t1 = t0 + r.seconds
-    out = messages(r, t0, t1, prob, kubecheck.load().kc_build_info().decode(), kubecheck.device_count())
+    out = messages(r, t0, t1, prob, kubecheck.load().kc_build_info().decode(), kubecheck.device_count(),
+                   parsed["symmetry"])
     if not props or r.error is not None:
         for code, cls, body in out:
             print(msg(code, body, cls, a.tool), flush=True)
