@@ -15,6 +15,7 @@
 #include "../../include/kubecheck.h"
 #include "coldset.h"
 #include "kc_common.h"
+#include "selftest_util.h"
 
 namespace kc {
 namespace {
@@ -27,12 +28,7 @@ struct ColdHarness {
   bool failed = false;              // an add_run failed: no probe / all_keys until clear
 };
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
+using selftest::DevBuf;
 
 __global__ void k_cold_key_selftest(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t n, int unkey) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/kubecheck.h"
+#include "claim_launch.h"
 #include "coldset.h"
 #include "engine.h"
 #include "engine_kernels.h"
@@ -179,19 +180,18 @@ constexpr uint64_t kMaxChunk = (1ull << 27) - 256;
 template <class M>
 class EngineT final : public EngineBase {
   using State = typename M::State;
+  OwnedStream st_;   // (first: destroyed after every buffer below)
 
  public:
   explicit EngineT(const kc_model_config& cfg) : EngineBase(cfg) {
     flags_ = flags_of(cfg);
     timing_ = cfg.timing == 2 ? 2 : (cfg.timing != 0 ? 1 : 0);
-    const char* ab = getenv("KC_ABLATE");
-    ablate_ = ab && ab[0] == '1';
+    ablate_ = env_flag("KC_ABLATE", false);
     if (ablate_) timing_ = 1;
     // the narrow-level kernel: on by default; off when the caller asks for
     // explicit chunks (the chunked wide path is what they exercise) or with
     // KC_NARROW=0
-    const char* nw = getenv("KC_NARROW");
-    narrow_on_ = cfg.chunk_states == 0 && !(nw && nw[0] == '0') && !ablate_;
+    narrow_on_ = cfg.chunk_states == 0 && env_flag("KC_NARROW", true) && !ablate_;
     // frontiers in the StateQueue (spill mode): the chunked wide path only
     queued_ = cfg.frontier_hbm_bytes > 0;
     if (queued_) narrow_on_ = false;
@@ -199,42 +199,33 @@ class EngineT final : public EngineBase {
     // the chunked wide path with tile offsets only
     spill_ = cfg.seen_hbm_bytes > 0;
     if (spill_) narrow_on_ = false;
-    const char* ts = getenv("KC_TSCAN");
-    tscan_ = spill_ || !(ts && ts[0] == '0');
-    const char* nb = getenv("KC_NARROW_BATCH");   // narrow levels enqueued per host sync (A/B)
-    if (nb && atoi(nb) > 0) narrow_batch_ = atoi(nb);
-    const char* tr = getenv("KC_TSCAN_REG");
-    tscan_reg_ = !(tr && tr[0] == '0');
-    const char* hc = getenv("KC_HEADCOPY");
-    headcopy_ = hc && hc[0] == '1';
+    tscan_ = spill_ || env_flag("KC_TSCAN", true);
+    // KC_NARROW_BATCH: narrow levels enqueued per host sync (A/B)
+    if (const uint64_t nb = env_u64("KC_NARROW_BATCH")) narrow_batch_ = (int)nb;
+    tscan_reg_ = env_flag("KC_TSCAN_REG", true);
+    headcopy_ = env_flag("KC_HEADCOPY", false);
     // deferred frontier (engine_kernels.h DeferArgs): the default wide path
     // (KC_DEFER=0: every level's k_emit builds and stores its new states)
-    const char* df = getenv("KC_DEFER");
-    defer_ = !(df && df[0] == '0') && !spill_ && !queued_ && !ablate_;
+    defer_ = env_flag("KC_DEFER", true) && !spill_ && !queued_ && !ablate_;
+    redo_on_ = env_flag("KC_DEFER_REDO", true);        // KC_DEFER_REDO=0: an anomaly redoes the run from Init
+    defer_direct_ = env_flag("KC_DEFER_DIRECT", true); // KC_DEFER_DIRECT=0: invariant anomalies are redone too (A/B)
     // KC_DEFER_SLACK: the capacity estimate's factor over the measured
     // successors per state (tests shrink it to force the exact-path redo)
-    const char* dr = getenv("KC_DEFER_REDO");      // KC_DEFER_REDO=0: an anomaly redoes the run from Init
-    redo_on_ = !(dr && dr[0] == '0');
-    const char* dd = getenv("KC_DEFER_DIRECT");    // KC_DEFER_DIRECT=0: invariant anomalies are redone too (A/B)
-    defer_direct_ = !(dd && dd[0] == '0');
     const char* ds = getenv("KC_DEFER_SLACK");
     if (ds && atof(ds) > 0) defer_slack_ = atof(ds);
     if (defer_) tscan_ = true;    // the link emit takes the tile offsets
     // KC_FIRST_CLAIM=1: first-claim mode (k_claim FIRST) on the in-HBM wide
     // path: the first inserter of a fingerprint wins, no settle passes (decided
     // after the tile scan is, which it needs; kc_result.claim_mode reports it)
-    const char* fc = getenv("KC_FIRST_CLAIM");
-    first_claim_ = (cfg.first_claim || (fc && fc[0] == '1')) && tscan_ && !spill_ && !queued_;
+    first_claim_ = (cfg.first_claim || env_flag("KC_FIRST_CLAIM", false)) && tscan_ && !spill_ && !queued_;
     // (first-claim mode writes no claim words, so no level's inserts can be
     // dropped: a deferred-frontier capacity anomaly redoes the run from Init;
     // an Assert or deadlock key is reported directly, as on the exact path)
     if (first_claim_) redo_on_ = false;
     // its ClaimSet holds fp words only (8-B slots: half the table to clear);
     // KC_CLAIM_COMPACT=0 keeps 16-B slots (A/B)
-    const char* cc = getenv("KC_CLAIM_COMPACT");
-    cs_.compact = first_claim_ && !(cc && cc[0] == '0');
-    const char* ck = getenv("KC_CHUNK_SCAN");
-    chunk_scan_ = !(ck && ck[0] == '0');
+    cs_.compact = first_claim_ && env_flag("KC_CLAIM_COMPACT", true);
+    chunk_scan_ = env_flag("KC_CHUNK_SCAN", true);
   }
   ~EngineT() override { release(); }
 
@@ -252,14 +243,12 @@ class EngineT final : public EngineBase {
       return -EINVAL;
     }
     KC_HIP_TRY(hipSetDevice(cfg_.device));
-    KC_HIP_TRY(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-    KC_HIP_TRY(hipMalloc(&d_ctr_, sizeof(Counters)));
-    KC_HIP_TRY(hipHostMalloc(&h_ctr_, sizeof(Counters)));
-    KC_HIP_TRY(hipMalloc(&d_ns_, sizeof(NarrowCtl)));
-    KC_HIP_TRY(hipHostMalloc(&h_ns_, sizeof(NarrowCtl)));
-    if (narrow_on_) {
-      KC_HIP_TRY(hipMalloc(&d_nsc_, sizeof(NarrowScratch)));
-    }
+    KC_HIP_TRY(hipStreamCreateWithFlags(&st_.s, hipStreamNonBlocking));
+    KC_TRY(d_ctr_.alloc(1));
+    KC_TRY(h_ctr_.alloc(1));
+    KC_TRY(d_ns_.alloc(1));
+    KC_TRY(h_ns_.alloc(1));
+    if (narrow_on_) KC_TRY(d_nsc_.alloc(1));
     return 0;
   }
 
@@ -284,8 +273,86 @@ class EngineT final : public EngineBase {
     return rc;
   }
 
+  // Where the BFS stands at the top of a level.
+  // Deferred frontier (defer_now_): `mat` = cur_ holds this level's states.
+  // Otherwise the level's k_claim rebuilds them from the previous frontier
+  // (next_, which starts at global index prev_gidx) and the links the
+  // previous level's emit wrote; `cand` is then unknown and the level's
+  // buffers are sized from `ratio`, the last measured successors per state.
+  struct LevelCursor {
+    uint64_t n = 0, level_gidx = 0, cand = 0, cand_total = 0, prev_gidx = 0;
+    int level = 1;
+    bool mat = true;
+    double ratio = 1.0;
+  };
+  // What a level's launches share, fixed when its buffers are sized.
+  struct LevelPlan {
+    bool dfr = false;            // this level runs deferred (emits links, not states)
+    bool use_link = false;       // links in HBM (the trace may be host memory)
+    uint64_t bound = 0, next_gidx = 0, link_cap = ~0ull;
+    uint32_t succ_level = 0;     // BFS level of the successors
+    DeferArgs df;
+  };
+  // a step's answer beyond "go on" (0) and an error (< 0)
+  static constexpr int kRunDone = 1;     // the result is complete (an error of the model was reported)
+  static constexpr int kGoWide = 2;      // the narrow kernel took no level: this one runs wide
+
   int run_once(kc_result* res) {
     KC_HIP_TRY(hipSetDevice(cfg_.device));
+    reset_run(res);
+    LevelCursor c;
+    std::vector<State> init;
+    int rc = seed_init(res, c, init);
+    if (rc) return rc < 0 ? rc : 0;
+
+    if (queued_) return run_queued(res, c.n, c.cand, init);
+
+    // default: one chunk per level; chunk_states bounds the per-chunk
+    // buffers.  Claims are level-global (keys grow with the parent index),
+    // so a chunk's winners are final once its own claim pass is done.
+    // per-level counter fields: err_key = ~0, the rest 0 (act_* are cumulative)
+    hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_.p);
+    // <= 2^27 parents per chunk: the chunk's scan runs on int counts and its
+    // offsets are u32 (at most 32 new states per parent: < 2^32 per chunk)
+    const uint64_t chunk =
+        (std::min<uint64_t>(cfg_.chunk_states ? cfg_.chunk_states : kMaxChunk, kMaxChunk) + 255) / 256 * 256;
+    c.ratio = c.n ? (double)c.cand / (double)c.n : 1.0;
+    pc_valid_ = false;                 // pc_prev_ holds the previous frontier's plans
+    while (c.n > 0) {
+      if (cfg_.max_levels && c.level >= cfg_.max_levels) break;
+      if (narrow_on_ && c.n <= (uint64_t)NARROW_MAX &&
+          (c.mat || (double)c.n * c.ratio <= 1.25 * (double)NARROW_CAND_MAX)) {
+        rc = narrow_levels(res, c);
+        if (rc < 0) return rc;
+        if (rc == kRunDone) return 0;
+        if (rc != kGoWide) continue;
+        // not even one level fitted (buffer room): this level goes wide
+      }
+      LevelPlan lp;
+      KC_TRY(size_level(res, c, chunk, lp));
+      for (uint64_t start = 0, cn = 0; start < c.n; start += cn) {
+        cn = std::min(chunk, c.n - start);
+        // seen-set spill: a chunk whose insertions fit the hot table (may flush it)
+        if (spill_) KC_TRY(spill_cut(cur_ + start, cn, &cn));
+        ++res->levels_chunks;
+        KC_TRY(launch_chunk(c, lp, start, cn));
+      }
+      rc = close_level(res, c, lp);
+      if (rc < 0) return rc;
+      if (rc == kRunDone) return 0;
+    }
+    // the last, unexpanded level (max_levels): its states' invariants
+    if (!c.mat && c.n) KC_TRY(materialize(c));
+    last_level_ = res->nlevels;
+    last_n_ = c.n;
+    finish(res, c.n);
+    if (ablate_) KC_TRY(ablate_report());
+    return 0;
+  }
+
+  // ---- the steps of run_once
+
+  void reset_run(kc_result* res) {
     memset(res, 0, sizeof *res);
     res->err_action = res->err_self = res->err_invariant = -1;
     res->claim_mode = first_claim_ ? 1 : 0;
@@ -298,15 +365,18 @@ class EngineT final : public EngineBase {
     narrow_levels_ = 0;
     exact_until_ = 0;
     for (auto& v : snap_lv_) v = -1;
-    for (auto& h : hs_) h.level = -1;
+    for (auto& h : hs_) h.c.level = -1;
     for (auto& v : succ_lv_) v = -1;
-    const auto t0 = std::chrono::steady_clock::now();
+    t0_ = std::chrono::steady_clock::now();
+  }
 
-    // ---- Init (KubeAPI.tla:455-469), on the host: 2^NC states
-    // (under symmetry the fingerprint is the orbit's: of the Init states of
-    // one orbit the first is kept, the others count as generated only)
+  // ---- Init (KubeAPI.tla:455-469), on the host: 2^NC states into cur_, the
+  // seen-set and the trace; their invariants.  c: level 1.  kRunDone: an
+  // Init state violates an invariant (reported).
+  // (under symmetry the fingerprint is the orbit's: of the Init states of
+  // one orbit the first is kept, the others count as generated only)
+  int seed_init(kc_result* res, LevelCursor& c, std::vector<State>& init) {
     const int ni_all = M::num_init();
-    std::vector<State> init;
     std::vector<uint64_t> fps;
     uint64_t cand = 0;
     for (int k = 0; k < ni_all; ++k) {
@@ -329,29 +399,27 @@ class EngineT final : public EngineBase {
     } else {
       KC_TRY(cs_.init(fp_slots, st_));
     }
-    KC_TRY(grow_buffer(cur_, cur_cap_, (uint64_t)ni, false, st_));
-    KC_TRY(grow_trace((uint64_t)ni + cand, false));
+    KC_TRY(cur_.grow((uint64_t)ni, st_));
+    KC_TRY(tf_.grow(cfg_.trace_host, (uint64_t)ni + cand, st_, false));
     KC_HIP_TRY(hipMemcpyAsync(cur_, init.data(), ni * sizeof(State), hipMemcpyHostToDevice, st_));
     // (the Init fingerprints' device buffers are kept across runs: a
     // hipMalloc / hipFree pair per run cost a device-wide sync)
-    KC_TRY(grow_buffer(init_fps_, init_fps_cap_, (uint64_t)ni, false, st_));
-    KC_TRY(grow_buffer(init_res_, init_res_cap_, (uint64_t)ni, false, st_));
-    uint64_t* const d_fps = init_fps_;
-    int* const d_res = init_res_;
-    KC_HIP_TRY(hipMemcpyAsync(d_fps, fps.data(), ni * 8, hipMemcpyHostToDevice, st_));
-    launch_claimset_insert_list(d_fps, (uint64_t)ni, cs_, 1u, d_res, st_);
+    KC_TRY(init_fps_.grow((uint64_t)ni, st_));
+    KC_TRY(init_res_.grow((uint64_t)ni, st_));
+    KC_HIP_TRY(hipMemcpyAsync(init_fps_, fps.data(), ni * 8, hipMemcpyHostToDevice, st_));
+    launch_claimset_insert_list(init_fps_.p, (uint64_t)ni, cs_, 1u, init_res_.p, st_);
     std::vector<int> ires(ni);
-    KC_HIP_TRY(hipMemcpyAsync(ires.data(), d_res, ni * sizeof(int), hipMemcpyDeviceToHost, st_));
+    KC_HIP_TRY(hipMemcpyAsync(ires.data(), init_res_, ni * sizeof(int), hipMemcpyDeviceToHost, st_));
     std::vector<unsigned long long> ipar(ni, ~0ull);
     std::vector<uint8_t> iord(ni);
     for (int k = 0; k < ni; ++k) iord[k] = (uint8_t)k;
     if (cfg_.trace_host) {
       KC_HIP_TRY(hipStreamSynchronize(st_));
-      memcpy(parent_, ipar.data(), ni * 8);
-      memcpy(ord_, iord.data(), ni);
+      memcpy(tf_.parent(), ipar.data(), ni * 8);
+      memcpy(tf_.ord(), iord.data(), ni);
     } else {
-      KC_HIP_TRY(hipMemcpyAsync(parent_, ipar.data(), ni * 8, hipMemcpyHostToDevice, st_));
-      KC_HIP_TRY(hipMemcpyAsync(ord_, iord.data(), ni, hipMemcpyHostToDevice, st_));
+      KC_HIP_TRY(hipMemcpyAsync(tf_.parent(), ipar.data(), ni * 8, hipMemcpyHostToDevice, st_));
+      KC_HIP_TRY(hipMemcpyAsync(tf_.ord(), iord.data(), ni, hipMemcpyHostToDevice, st_));
     }
     KC_HIP_TRY(hipStreamSynchronize(st_));
     for (int k = 0; k < ni; ++k) {
@@ -364,15 +432,19 @@ class EngineT final : public EngineBase {
     hot_count_ = ni;
     KC_HIP_TRY(hipMemsetAsync(d_ctr_, 0, sizeof(Counters), st_));
     if (d_ovf_cnt_) KC_HIP_TRY(hipMemsetAsync(d_ovf_cnt_, 0, 8, st_));
+    // k_chunk_scan's chunk sums: zero when a level starts (a run that
+    // stopped between k_claim and the scan left them dirty)
+    if (csum_) KC_HIP_TRY(hipMemsetAsync(csum_, 0, csum_.cap * sizeof(uint32_t), st_));
     if (defer_now_) KC_TRY(counter_snap(0));
     res->init = ni_all;
     res->generated = ni_all;
     res->distinct = ni;
     init_states_ = init;
 
-    uint64_t n = ni, level_gidx = 0, cand_total = 0;
-    int level = 1;
-    res->level_width[0] = n;
+    c = LevelCursor{};
+    c.n = ni;
+    c.cand = cand;
+    res->level_width[0] = c.n;
     res->nlevels = 1;
     // invariants of the initial states
     for (int k = 0; k < ni; ++k) {
@@ -383,389 +455,367 @@ class EngineT final : public EngineBase {
         res->err_level = 1;
         trace_.push_back(init[k]);
         res->trace_len = 1;
-        finish(res, t0, n);
-        return 0;
+        finish(res, c.n);
+        return kRunDone;
       }
     }
+    return 0;
+  }
 
-    if (queued_) return run_queued(res, t0, n, cand, init);
-
-    // default: one chunk per level; chunk_states bounds the per-chunk
-    // buffers.  Claims are level-global (keys grow with the parent index),
-    // so a chunk's winners are final once its own claim pass is done.
-    // per-level counter fields: err_key = ~0, the rest 0 (act_* are cumulative)
-    hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_);
-    // <= 2^27 parents per chunk: the chunk's scan runs on int counts and its
-    // offsets are u32 (at most 32 new states per parent: < 2^32 per chunk)
-    const uint64_t chunk =
-        (std::min<uint64_t>(cfg_.chunk_states ? cfg_.chunk_states : kMaxChunk, kMaxChunk) + 255) / 256 * 256;
-    // Deferred frontier (defer_now_): `mat` = cur_ holds this level's states.
-    // Otherwise the level's k_claim rebuilds them from the previous frontier
-    // (next_, which starts at global index prev_gidx) and the links the
-    // previous level's emit wrote; `cand` is then unknown and the level's
-    // buffers are sized from `ratio`, the last measured successors per state.
-    bool mat = true;
-    uint64_t prev_gidx = 0;
-    double ratio = n ? (double)cand / (double)n : 1.0;
-    pc_valid_ = false;                 // pc_prev_ holds the previous frontier's plans
-    while (n > 0) {
-      if (cfg_.max_levels && level >= cfg_.max_levels) break;
-      if (narrow_on_ && n <= (uint64_t)NARROW_MAX &&
-          (mat || (double)n * ratio <= 1.25 * (double)NARROW_CAND_MAX)) {
-        // ---- narrow levels: one single-workgroup launch runs as many
-        // levels as fit (engine_narrow.h); the host takes over at the first
-        // level it cannot run.  It needs the states and their exact
-        // successor count: a deferred frontier is materialised first.
-        if (!mat) {
-          KC_TRY(materialize(n, level_gidx, prev_gidx, cand, cand_total));
-          mat = true;
-          KC_TRY(counter_snap(level - 1));     // (k_materialize counted the states' actions)
-        }
-        pc_valid_ = false;
-        int stop = cfg_.max_levels;
-        if (capture_level_ >= level + 1 && (stop == 0 || capture_level_ - 1 < stop)) stop = capture_level_ - 1;
-        NarrowRun nr;
-        KC_TRY(run_narrow(n, level, level_gidx, cand, stop, nr));
-        res->distinct += nr.new_total;
-        for (int L = level; L < nr.level; ++L) {
-          if (L >= KC_MAX_LEVELS) {
-            set_error("kubecheck: more than %d levels", KC_MAX_LEVELS);
-            return -ENOMEM;
-          }
-          res->level_width[L] = h_ns_->widths[L];
-        }
-        if (nr.levels) res->peak_frontier = std::max<uint64_t>(res->peak_frontier, std::max(n, nr.peak));
-        level = nr.level;
-        level_gidx = nr.level_gidx;
-        n = nr.n;
-        cand = nr.cand;
-        if (nr.levels) res->nlevels = n ? level : level - 1;
-        if (defer_now_ && nr.levels && nr.reason != NX_ERROR) KC_TRY(counter_snap(level - 1));
-        if (nr.reason == NX_ERROR) {
-          KC_TRY(report_error(res, h_ns_->err_key, level, level_gidx, n));
-          finish(res, t0, 0);
-          return 0;
-        }
-        if (nr.levels > 0 || n == 0) continue;
-        // not even one level fitted (buffer room): this level goes wide
-      }
-      if (n >= (1ull << 32)) {
-        set_error("kubecheck: level wider than 2^32 states");
+  // ---- narrow levels: one single-workgroup launch runs as many levels as
+  // fit (engine_narrow.h); the host takes over at the first level it cannot
+  // run.  It needs the states and their exact successor count: a deferred
+  // frontier is materialised first.  kGoWide: no level ran and there are
+  // states left.
+  int narrow_levels(kc_result* res, LevelCursor& c) {
+    if (!c.mat) {
+      KC_TRY(materialize(c));
+      c.mat = true;
+      KC_TRY(counter_snap(c.level - 1));     // (k_materialize counted the states' actions)
+    }
+    pc_valid_ = false;
+    int stop = cfg_.max_levels;
+    if (capture_level_ >= c.level + 1 && (stop == 0 || capture_level_ - 1 < stop)) stop = capture_level_ - 1;
+    const int level0 = c.level;
+    const uint64_t n0 = c.n;
+    NarrowRun nr;
+    KC_TRY(run_narrow(c, stop, nr));
+    res->distinct += nr.new_total;
+    for (int L = level0; L < c.level; ++L) {
+      if (L >= KC_MAX_LEVELS) {
+        set_error("kubecheck: more than %d levels", KC_MAX_LEVELS);
         return -ENOMEM;
       }
-      // capacity for this level's output: cand is exact (next_cand of the
-      // previous level) when the states are materialised; a deferred level's
-      // is estimated, and a level past the estimate (DF_CAPACITY, a full
-      // candidate list or table) is redone on the exact path
-      const bool dfr = defer_now_ && level > exact_until_;
-      if (mat && n) ratio = std::max(1.0, (double)cand / (double)n);
-      const uint64_t bound = mat ? cand
-                                 : std::min<uint64_t>((uint64_t)((double)n * ratio * defer_slack_) + 4096,
-                                                      (uint64_t)M::MAXSUCC * n);
-      const bool use_link = !cfg_.keep_trace || cfg_.trace_host;   // links in HBM (the trace may be host memory)
-      if (dfr) {
-        if (!mat) KC_TRY(grow_buffer(cur_, cur_cap_, n, false, st_));   // (free: the previous frontier is in next_)
-        KC_TRY(grow_buffer(pc_cur_, pc_cur_cap_, n, false, st_));
-        if (use_link) KC_TRY(grow_buffer(link_next_, link_next_cap_, std::max<uint64_t>(bound, 1), false, st_));
+      res->level_width[L] = h_ns_->widths[L];
+    }
+    if (nr.levels) res->peak_frontier = std::max<uint64_t>(res->peak_frontier, std::max(n0, nr.peak));
+    if (nr.levels) res->nlevels = c.n ? c.level : c.level - 1;
+    if (defer_now_ && nr.levels && nr.reason != NX_ERROR) KC_TRY(counter_snap(c.level - 1));
+    if (nr.reason == NX_ERROR) {
+      KC_TRY(report_error(res, h_ns_->err_key, c.level, c.level_gidx, c.n));
+      finish(res, 0);
+      return kRunDone;
+    }
+    return (nr.levels > 0 || c.n == 0) ? 0 : kGoWide;
+  }
+
+  // The per-chunk buffers of a level whose chunks have <= cmax parents and
+  // whose successors number <= bound (run_once and run_queued).
+  int size_chunk_buffers(uint64_t cmax, uint64_t bound, int level, uint64_t n) {
+    const uint64_t tiles = (cmax + CLAIM_TILE - 1) / CLAIM_TILE;
+    KC_TRY(rcount_.grow(tiles, st_));
+    if (tscan_) {
+      KC_TRY(ttot_.grow(tiles + 4, st_));
+      KC_TRY(toff_.grow(tiles + 4, st_));
+      if (first_claim_ && chunk_scan_) {
+        const uint64_t old = csum_.cap;
+        KC_TRY(csum_.grow(tiles / CSUM_TILES + 4, st_));
+        if (csum_.cap != old) KC_HIP_TRY(hipMemsetAsync(csum_, 0, csum_.cap * sizeof(uint32_t), st_));
+      }
+    }
+    KC_TRY(rec_fp_.grow(tiles * CLAIM_RCAP, st_));
+    KC_TRY(rec_lk_.grow(tiles * CLAIM_RCAP, st_));
+    KC_TRY(cand_overflow(bound, level, n));
+    KC_TRY(newmask_.grow(cmax, st_));
+    return offsets_.grow(cmax, st_);
+  }
+
+  // Capacity for this level's output, and what its launches share (lp).
+  int size_level(kc_result* res, LevelCursor& c, uint64_t chunk, LevelPlan& lp) {
+    if (c.n >= (1ull << 32)) {
+      set_error("kubecheck: level wider than 2^32 states");
+      return -ENOMEM;
+    }
+    // cand is exact (next_cand of the previous level) when the states are
+    // materialised; a deferred level's is estimated, and a level past the
+    // estimate (DF_CAPACITY, a full candidate list or table) is redone on
+    // the exact path
+    lp.dfr = defer_now_ && c.level > exact_until_;
+    if (c.mat && c.n) c.ratio = std::max(1.0, (double)c.cand / (double)c.n);
+    lp.bound = c.mat ? c.cand
+                     : std::min<uint64_t>((uint64_t)((double)c.n * c.ratio * defer_slack_) + 4096,
+                                          (uint64_t)M::MAXSUCC * c.n);
+    lp.use_link = !cfg_.keep_trace || cfg_.trace_host;
+    if (lp.dfr) {
+      if (!c.mat) KC_TRY(cur_.grow(c.n, st_));   // (free: the previous frontier is in next_)
+      KC_TRY(pc_cur_.grow(c.n, st_));
+      if (lp.use_link) KC_TRY(link_next_.grow(std::max<uint64_t>(lp.bound, 1), st_));
+    } else {
+      KC_TRY(next_.grow(c.cand ? c.cand : 1, st_));
+    }
+    lp.next_gidx = c.level_gidx + c.n;
+    if (cfg_.keep_trace) KC_TRY(tf_.grow(cfg_.trace_host, lp.next_gidx + lp.bound + 1, st_, true));
+    // (a deferred level reserves for 16 new states per parent at least:
+    // (count + 16 n) * 2 <= capacity keeps even MAXSUCC = 32 per parent
+    // from filling the table, whatever the estimate)
+    if (!spill_) KC_TRY(cs_.reserve(c.mat ? lp.bound : std::max<uint64_t>(lp.bound, 16 * c.n), st_));
+    KC_TRY(size_chunk_buffers(std::min(c.n, chunk), lp.bound, c.level, c.n));
+    lp.df = c.mat ? DeferArgs{} : defer_args(c.level_gidx, c.prev_gidx);
+    if (lp.dfr) lp.df.counts_out = pc_cur_;   // this level's plans, for the next level's rebuild
+    if (!c.mat) res->deferred_states += c.n;
+    lp.link_cap = ~0ull;
+    if (lp.dfr) {
+      if (lp.use_link) lp.link_cap = link_next_.cap;
+      if (cfg_.keep_trace) lp.link_cap = std::min<uint64_t>(lp.link_cap, tf_.cap() - lp.next_gidx);
+    }
+    if (defer_now_)      // (after this level's ClaimSet growth: a rehash later rules out a redo from here)
+      hs_[c.level % 3] = HostSnap{c, cs_.count, res->distinct, res->peak_frontier, cs_.nslots, res->nlevels};
+    lp.succ_level = (uint32_t)c.level + 1;
+    return 0;
+  }
+
+  ClaimBufs claim_bufs() const { return ClaimBufs{abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_}; }
+  // k_claim<M, ABL, false, 0, false, FIRST, C8> over cn parents at cur (the
+  // chunk that begins at parent `start` of the level)
+  template <int ABL = 0, bool FIRST = false, bool C8 = false>
+  void claim(const State* cur, uint64_t cn, uint64_t start, unsigned tiles, uint32_t succ_level, const ShardArgs& sh,
+             const DeferArgs& df = DeferArgs{}) {
+    launch_claim<M, ABL, false, 0, false, FIRST, C8>(st_, tiles, 0, cur, cn, start, flags_, cfg_.check_deadlock, cs_,
+                                                     succ_level, claim_bufs(), sh, df);
+  }
+
+  // One chunk's launches: parents [start, start + cn) of the level.
+  int launch_chunk(const LevelCursor& c, const LevelPlan& lp, uint64_t start, uint64_t cn) {
+    const unsigned grid = (unsigned)((cn + 255) / 256);
+    const unsigned tiles = (unsigned)((cn + CLAIM_TILE - 1) / CLAIM_TILE);
+    const uint32_t succ_level = lp.succ_level;
+    // first-claim levels with the link emit: tile counts summed per chunk
+    // of CSUM_TILES tiles by k_claim, k_chunk_scan over the chunks
+    // (KC_CHUNK_SCAN=0: k_tile_scan over every tile)
+    const bool cscan = first_claim_ && chunk_scan_ && tscan_ && lp.dfr;
+    const unsigned nchunk = (tiles + CSUM_TILES - 1) / CSUM_TILES;
+    timed(KK_EXPAND, [&] {
+      if (first_claim_) {
+        ShardArgs fa = claim_args_;
+        fa.ttot = ttot_;
+        if (cscan) fa.csum = csum_;
+        if (cs_.compact)
+          claim<0, true, true>(cur_ + start, cn, start, tiles, succ_level, fa, lp.df);
+        else
+          claim<0, true>(cur_ + start, cn, start, tiles, succ_level, fa, lp.df);
       } else {
-        KC_TRY(grow_buffer(next_, next_cap_, cand ? cand : 1, false, st_));
+        claim(cur_ + start, cn, start, tiles, succ_level, claim_args_, lp.df);
       }
-      const uint64_t next_gidx = level_gidx + n;
-      if (cfg_.keep_trace) KC_TRY(grow_trace(next_gidx + bound + 1, true));
-      // (a deferred level reserves for 16 new states per parent at least:
-      // (count + 16 n) * 2 <= capacity keeps even MAXSUCC = 32 per parent
-      // from filling the table, whatever the estimate)
-      if (!spill_) KC_TRY(cs_.reserve(mat ? bound : std::max<uint64_t>(bound, 16 * n), st_));
-      {
-        const uint64_t tiles = (std::min(n, chunk) + CLAIM_TILE - 1) / CLAIM_TILE;
-        KC_TRY(grow_buffer(rcount_, rcount_cap_, tiles, false, st_));
-        if (tscan_) {
-          KC_TRY(grow_buffer(ttot_, ttot_cap_, tiles + 4, false, st_));
-          KC_TRY(grow_buffer(toff_, toff_cap_, tiles + 4, false, st_));
-          if (first_claim_ && chunk_scan_) {
-            const uint64_t old = csum_cap_;
-            KC_TRY(grow_buffer(csum_, csum_cap_, tiles / CSUM_TILES + 4, false, st_));
-            if (csum_cap_ != old) KC_HIP_TRY(hipMemsetAsync(csum_, 0, csum_cap_ * sizeof(uint32_t), st_));
-          }
-        }
-        KC_TRY(grow_buffer(rec_fp_, rec_fp_cap_, tiles * CLAIM_RCAP, false, st_));
-        KC_TRY(grow_buffer(rec_lk_, rec_lk_cap_, tiles * CLAIM_RCAP, false, st_));
-        KC_TRY(cand_overflow(bound, level, n));
-      }
-      KC_TRY(grow_buffer(newmask_, mask_cap_, std::min(n, chunk), false, st_));
-      DeferArgs df = mat ? DeferArgs{} : defer_args(level_gidx, prev_gidx);
-      if (dfr) df.counts_out = pc_cur_;   // this level's plans, for the next level's rebuild
-      if (!mat) res->deferred_states += n;
-      uint64_t link_cap = ~0ull;
-      if (dfr) {
-        if (use_link) link_cap = link_next_cap_;
-        if (cfg_.keep_trace) link_cap = std::min<uint64_t>(link_cap, std::min(par_cap_, ord_cap_) - next_gidx);
-      }
-      KC_TRY(grow_buffer(offsets_, off_cap_, std::min(n, chunk), false, st_));
-      if (defer_now_)      // (after this level's ClaimSet growth: a rehash later rules out a redo from here)
-        hs_[level % 3] = HostSnap{level, n, level_gidx, cand, prev_gidx, cs_.count, res->distinct,
-                                  res->peak_frontier, cand_total, cs_.nslots, res->nlevels, mat, ratio};
-      const uint32_t succ_level = (uint32_t)level + 1;   // BFS level of the successors
-      for (uint64_t start = 0, cn = 0; start < n; start += cn) {
-        cn = std::min(chunk, n - start);
-        // seen-set spill: a chunk whose insertions fit the hot table (may flush it)
-        if (spill_) KC_TRY(spill_cut(cur_ + start, cn, &cn));
-        ++res->levels_chunks;
-        const unsigned grid = (unsigned)((cn + 255) / 256);
-        const unsigned tiles = (unsigned)((cn + CLAIM_TILE - 1) / CLAIM_TILE);
-        // first-claim levels with the link emit: tile counts summed per chunk
-        // of CSUM_TILES tiles by k_claim, k_chunk_scan over the chunks
-        // (KC_CHUNK_SCAN=0: k_tile_scan over every tile)
-        const bool cscan = first_claim_ && chunk_scan_ && tscan_ && dfr;
-        const unsigned nchunk = (tiles + CSUM_TILES - 1) / CSUM_TILES;
-        timed(KK_EXPAND, [&] {
-          if (first_claim_) {
-            ShardArgs fa = claim_args_;
-            fa.ttot = ttot_;
-            if (cscan) fa.csum = csum_;
-            if (cs_.compact)
-              hipLaunchKernelGGL((k_claim<M, 0, false, 0, false, true, true>), dim3(tiles), dim3(CLAIM_TILE), 0, st_,
-                                 cur_ + start, cn, start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots, succ_level,
-                                 abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, fa, df);
-            else
-              hipLaunchKernelGGL((k_claim<M, 0, false, 0, false, true>), dim3(tiles), dim3(CLAIM_TILE), 0, st_,
-                                 cur_ + start, cn, start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots, succ_level,
-                                 abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, fa, df);
-          } else {
-            hipLaunchKernelGGL(k_claim<M>, dim3(tiles), dim3(CLAIM_TILE), 0, st_, cur_ + start, cn,
-                               start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots, succ_level,
-                               abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, claim_args_, df);
-          }
-        });
-        if (ablate_) {
-          KC_TRY(grow_buffer(abl_mask_, abl_cap_, cn, false, st_));
-          timed(KA_LDS, [&] {
-            hipLaunchKernelGGL((k_claim<M, 1>), dim3(tiles), dim3(CLAIM_TILE), 0, st_, cur_ + start,
-                               cn, start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                               succ_level, abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, claim_args_);
-          });
-          timed(KA_COMPUTE, [&] {
-            hipLaunchKernelGGL((k_claim<M, 2>), dim3(tiles), dim3(CLAIM_TILE), 0, st_, cur_ + start,
-                               cn, start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                               succ_level, abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, claim_args_);
-          });
-          timed(KA_PLAN, [&] {
-            hipLaunchKernelGGL((k_claim<M, 3>), dim3(tiles), dim3(CLAIM_TILE), 0, st_, cur_ + start,
-                               cn, start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                               succ_level, abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, claim_args_);
-          });
-          timed(KA_FPCHEAP, [&] {
-            hipLaunchKernelGGL((k_claim<M, 4>), dim3(tiles), dim3(CLAIM_TILE), 0, st_, cur_ + start,
-                               cn, start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                               succ_level, abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, claim_args_);
-          });
-          timed(KA_NOAPPLY, [&] {
-            hipLaunchKernelGGL((k_claim<M, 5>), dim3(tiles), dim3(CLAIM_TILE), 0, st_, cur_ + start,
-                               cn, start, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                               succ_level, abl_mask_, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, claim_args_);
-          });
-        }
-        // (a small chunk: the overflow list's pass B inside the tile scan's launch)
-        const bool fuse = tscan_ && cn <= FUSE_OVF_SCAN_MAX && !first_claim_;
-        if (!first_claim_)
-          timed(KK_RESOLVE,
-                [&] { launch_settle(cn, start, tiles, succ_level, tscan_ ? ttot_ : (uint32_t*)nullptr, fuse); });
-        if (cscan) {
-          timed(KK_SCAN, [&] {
-            hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, csum_, nchunk, toff_, tscan_reg_);
-          });
-        } else if (tscan_) {
-          timed(KK_SCAN, [&] {
-            if (fuse)
-              hipLaunchKernelGGL(k_ovf_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, claim_args_.ovf, cn, start,
-                                 cs_.t, cs_.nslots, succ_level, newmask_, d_ctr_, ClaimKeys(0u), ttot_, tiles, toff_,
-                                 tscan_reg_);
-            else
-              hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ttot_, tiles, toff_, tscan_reg_);
-          });
-        } else {
-        size_t tmp_bytes = 0;
-        const hipcub::TransformInputIterator<uint32_t, NewCount, const uint32_t*> newcnt(newmask_, NewCount());
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, newcnt, offsets_, (int)cn, st_));
-        KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-        hipError_t scan_err = hipSuccess;
-        timed(KK_SCAN, [&] {
-          scan_err = hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, newcnt, offsets_, (int)cn, st_);
-        });
-        KC_HIP_TRY(scan_err);
-        }
-        if (spill_) KC_TRY(spill_check(cur_ + start, cn, tiles));
-        const uint32_t* toff = tscan_ ? toff_ : nullptr;
-        if (ablate_) {
-          // cut-down k_emit variants on scratch counters, before the real
-          // launch (which rewrites whatever they stored)
-          if (!d_ctr_abl_) KC_HIP_TRY(hipMalloc(&d_ctr_abl_, sizeof(Counters)));
-          KC_HIP_TRY(hipMemsetAsync(d_ctr_abl_, 0, sizeof(Counters), st_));
-          timed(KA_E1, [&] {
-            hipLaunchKernelGGL((k_emit<M, 1>), dim3(grid), dim3(256), 0, st_, cur_ + start, cn, start,
-                               flags_, newmask_, offsets_, next_, 0ull, level_gidx, next_gidx, parent_, ord_,
-                               cfg_.keep_trace, d_ctr_abl_, toff);
-          });
-          timed(KA_E2, [&] {
-            hipLaunchKernelGGL((k_emit<M, 2>), dim3(grid), dim3(256), 0, st_, cur_ + start, cn, start,
-                               flags_, newmask_, offsets_, next_, 0ull, level_gidx, next_gidx, parent_, ord_,
-                               cfg_.keep_trace, d_ctr_abl_, toff);
-          });
-          timed(KA_E3, [&] {
-            hipLaunchKernelGGL((k_emit<M, 3>), dim3(grid), dim3(256), 0, st_, cur_ + start, cn, start,
-                               flags_, newmask_, offsets_, next_, 0ull, level_gidx, next_gidx, parent_, ord_,
-                               cfg_.keep_trace, d_ctr_abl_, toff);
-          });
-        }
-        timed(KK_EMIT, [&] {
-          if (dfr)
-            hipLaunchKernelGGL(k_emit_links, dim3((tiles + EMIT_TPB - 1) / EMIT_TPB), dim3(256), 0, st_, cn, start,
-                               newmask_, toff_, level_gidx,
-                               next_gidx, cfg_.keep_trace ? parent_ : nullptr, cfg_.keep_trace ? ord_ : nullptr,
-                               use_link ? link_next_ : nullptr, link_cap, d_ctr_,
-                               cscan ? ttot_ : (const uint32_t*)nullptr);
-          else
-            hipLaunchKernelGGL(k_emit<M>, dim3(grid), dim3(256), 0, st_, cur_ + start, cn, start,
-                               flags_, newmask_, offsets_, next_, 0ull, level_gidx, next_gidx, parent_, ord_,
-                               cfg_.keep_trace, d_ctr_, toff);
-        });
-        const bool last = start + cn >= n;
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(K_ADVANCE_THREADS), 0, st_, offsets_, newmask_, cn, d_ctr_,
-                           tscan_ ? toff_ : (const uint32_t*)nullptr, (uint64_t)(cscan ? nchunk : tiles),
-                           last && !headcopy_ ? reinterpret_cast<unsigned long long*>(h_ctr_) : nullptr,
-                           claim_args_.ovf.count,
-                           last && defer_now_ && !headcopy_ ? d_snap_[level % 3].s : (CtrStripe*)nullptr);
-      }
-      KC_HIP_TRY(hipGetLastError());
-      if (headcopy_) {
-        KC_HIP_TRY(hipMemcpyAsync(h_ctr_, d_ctr_, kCtrHead, hipMemcpyDeviceToHost, st_));
-        hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_);   // next level's head
-      }
-      KC_HIP_TRY(hipStreamSynchronize(st_));
-      collect_times();
-      const Counters& c = *h_ctr_;
-      // a deferred level with anything to report: redo exactly, from the level
-      // the anomaly belongs to
-      // (first-claim mode: an Assert or deadlock key alone is reported below,
-      // from the states this k_claim rebuilt into cur_, exactly as the
-      // materialising path's k_claim of this level reports it — no redo)
-      const bool key_only = first_claim_ && !c.overflow && !c.batch_used && !c.defer_flags;
-      if (dfr && !key_only && (c.overflow || c.batch_used || c.err_key != ~0ull || c.defer_flags)) {
-        // an invariant violation among the states this level rebuilt is
-        // the previous level's error (its emit would have found it); the
-        // rest (Assert / deadlock keys of this level's parents, a capacity
-        // estimate too small) are this level's
-        if (c.defer_flags == DF_INVARIANT && !c.overflow && !c.batch_used && defer_direct_) {
-          // an invariant violation among this level's rebuilt states and
-          // nothing else: reported as the previous level's emit would have
-          // (no redo), unless the snapshots it needs are missing
-          const int rc = report_deferred_invariant(res, level, level_gidx, n);
-          if (rc < 0) return rc;
-          if (rc == 0) {
-            finish(res, t0, 0);
-            return 0;
-          }
-        }
-        const int X = (c.defer_flags & DF_INVARIANT) ? level - 1 : level;
-        const uint64_t dc_here = c.cand_total - cand_total;
-        if (!redo_from(X, level, mat, dc_here, res, n, level_gidx, cand, prev_gidx, cand_total, ratio)) return kDeferRetry;
-        level = X;
-        mat = true;
-        pc_valid_ = false;
-        continue;
-      }
-      if (c.overflow || c.batch_used) {
-        set_error("kubecheck: state with more than %d successors or full table", M::MAXSUCC);
+    });
+    if (ablate_) KC_TRY(ablate_claims(start, cn, tiles, succ_level));
+    // (a small chunk: the overflow list's pass B inside the tile scan's launch)
+    const bool fuse = tscan_ && cn <= FUSE_OVF_SCAN_MAX && !first_claim_;
+    if (!first_claim_)
+      timed(KK_RESOLVE,
+            [&] { launch_settle(cn, start, tiles, succ_level, tscan_ ? ttot_.p : (uint32_t*)nullptr, fuse); });
+    if (cscan) {
+      timed(KK_SCAN, [&] {
+        hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, csum_.p, nchunk, toff_.p, tscan_reg_);
+      });
+    } else if (tscan_) {
+      timed(KK_SCAN, [&] {
+        if (fuse)
+          hipLaunchKernelGGL(k_ovf_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, claim_args_.ovf, cn, start,
+                             cs_.t, cs_.nslots, succ_level, newmask_.p, d_ctr_.p, ClaimKeys(0u), ttot_.p, tiles,
+                             toff_.p, tscan_reg_);
+        else
+          hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ttot_.p, tiles, toff_.p, tscan_reg_);
+      });
+    } else {
+      KC_TRY(scan_newmask(cn));
+    }
+    if (spill_) KC_TRY(spill_check(cur_ + start, cn, tiles));
+    const uint32_t* toff = tscan_ ? toff_.p : nullptr;
+    // cut-down k_emit variants on scratch counters, before the real launch
+    // (which rewrites whatever they stored)
+    if (ablate_) KC_TRY(ablate_emits(c, lp, start, cn, grid, toff));
+    timed(KK_EMIT, [&] {
+      if (lp.dfr)
+        hipLaunchKernelGGL(k_emit_links, dim3((tiles + EMIT_TPB - 1) / EMIT_TPB), dim3(256), 0, st_, cn, start,
+                           newmask_.p, toff_.p, c.level_gidx, lp.next_gidx,
+                           cfg_.keep_trace ? tf_.parent() : nullptr, cfg_.keep_trace ? tf_.ord() : nullptr,
+                           lp.use_link ? link_next_.p : nullptr, lp.link_cap, d_ctr_.p,
+                           cscan ? ttot_.p : (const uint32_t*)nullptr);
+      else
+        hipLaunchKernelGGL(k_emit<M>, dim3(grid), dim3(256), 0, st_, cur_ + start, cn, start, flags_, newmask_.p,
+                           offsets_.p, next_.p, 0ull, c.level_gidx, lp.next_gidx, tf_.parent(), tf_.ord(),
+                           cfg_.keep_trace, d_ctr_.p, toff);
+    });
+    const bool last = start + cn >= c.n;
+    hipLaunchKernelGGL(k_advance, dim3(1), dim3(K_ADVANCE_THREADS), 0, st_, offsets_.p, newmask_.p, cn, d_ctr_.p,
+                       tscan_ ? toff_.p : (const uint32_t*)nullptr, (uint64_t)(cscan ? nchunk : tiles),
+                       last && !headcopy_ ? reinterpret_cast<unsigned long long*>(h_ctr_.p) : nullptr,
+                       claim_args_.ovf.count,
+                       last && defer_now_ && !headcopy_ ? d_snap_[c.level % 3].s : (CtrStripe*)nullptr);
+    return 0;
+  }
+
+  // KC_TSCAN=0 and the queued path: the per-parent hipcub scan of a chunk's
+  // new-state counts into offsets_
+  int scan_newmask(uint64_t cn) {
+    size_t tmp_bytes = 0;
+    const hipcub::TransformInputIterator<uint32_t, NewCount, const uint32_t*> newcnt(newmask_.p, NewCount());
+    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, newcnt, offsets_.p, (int)cn, st_));
+    KC_TRY(scan_tmp_.grow(tmp_bytes + 16, st_));
+    hipError_t scan_err = hipSuccess;
+    timed(KK_SCAN, [&] {
+      scan_err = hipcub::DeviceScan::ExclusiveSum(scan_tmp_.p, tmp_bytes, newcnt, offsets_.p, (int)cn, st_);
+    });
+    KC_HIP_TRY(scan_err);
+    return 0;
+  }
+
+  // After a level's width is known: its place in the result.
+  int record_level(kc_result* res, int level, uint64_t n) {
+    if (n) {
+      if (level > KC_MAX_LEVELS) {
+        set_error("kubecheck: more than %d levels", KC_MAX_LEVELS);
         return -ENOMEM;
       }
-      const uint64_t n_new = c.chunk_base;
-      cs_.count = spill_ ? hot_count_ : cs_.count + n_new;
-      res->peak_frontier = std::max<uint64_t>(res->peak_frontier, n);
-      if (c.err_key != ~0ull) {
-        KC_TRY(report_error(res, c.err_key, level, level_gidx, n));
-        res->distinct += n_new;
-        finish(res, t0, 0);
-        return 0;
+      res->level_width[level - 1] = n;
+      res->nlevels = level;
+    }
+    return 0;
+  }
+
+  // The level's close: head read-back, the redo decision, the error report,
+  // the frontier swap and the width bookkeeping.  0: c is the next level to
+  // run (after a redo: the level to run again).
+  int close_level(kc_result* res, LevelCursor& c, const LevelPlan& lp) {
+    const bool dfr = lp.dfr;
+    KC_HIP_TRY(hipGetLastError());
+    if (headcopy_) {
+      KC_HIP_TRY(hipMemcpyAsync(h_ctr_, d_ctr_, kCtrHead, hipMemcpyDeviceToHost, st_));
+      hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_.p);   // next level's head
+    }
+    KC_HIP_TRY(hipStreamSynchronize(st_));
+    collect_times();
+    const Counters& h = *h_ctr_;
+    // a deferred level with anything to report: redo exactly, from the level
+    // the anomaly belongs to
+    // (first-claim mode: an Assert or deadlock key alone is reported below,
+    // from the states this k_claim rebuilt into cur_, exactly as the
+    // materialising path's k_claim of this level reports it — no redo)
+    const bool key_only = first_claim_ && !h.overflow && !h.batch_used && !h.defer_flags;
+    if (dfr && !key_only && (h.overflow || h.batch_used || h.err_key != ~0ull || h.defer_flags)) {
+      // an invariant violation among the states this level rebuilt is
+      // the previous level's error (its emit would have found it); the
+      // rest (Assert / deadlock keys of this level's parents, a capacity
+      // estimate too small) are this level's
+      if (h.defer_flags == DF_INVARIANT && !h.overflow && !h.batch_used && defer_direct_) {
+        // an invariant violation among this level's rebuilt states and
+        // nothing else: reported as the previous level's emit would have
+        // (no redo), unless the snapshots it needs are missing
+        const int rc = report_deferred_invariant(res, c);
+        if (rc < 0) return rc;
+        if (rc == 0) {
+          finish(res, 0);
+          return kRunDone;
+        }
       }
+      const int X = (h.defer_flags & DF_INVARIANT) ? c.level - 1 : c.level;
+      const uint64_t dc_here = h.cand_total - c.cand_total;
+      if (!redo_from(X, dc_here, res, c)) return kDeferRetry;
+      pc_valid_ = false;
+      return 0;
+    }
+    if (h.overflow || h.batch_used) {
+      set_error("kubecheck: state with more than %d successors or full table", M::MAXSUCC);
+      return -ENOMEM;
+    }
+    const uint64_t n_new = h.chunk_base;
+    cs_.count = spill_ ? hot_count_ : cs_.count + n_new;
+    res->peak_frontier = std::max<uint64_t>(res->peak_frontier, c.n);
+    if (h.err_key != ~0ull) {
+      KC_TRY(report_error(res, h.err_key, c.level, c.level_gidx, c.n));
       res->distinct += n_new;
-      if (cfg_.verbose)
-        fprintf(stderr, "kubecheck: level %d width %llu -> %llu new, %llu distinct\n",
-                level, (unsigned long long)n, (unsigned long long)n_new,
-                (unsigned long long)res->distinct);
-      if (!dfr && capture_level_ == level + 1 && n_new) {
-        captured_.resize(n_new);
-        KC_HIP_TRY(hipMemcpy(captured_.data(), next_, n_new * sizeof(State), hipMemcpyDeviceToHost));
-      }
-      // successors counted this level: the new states' (materialising emit),
-      // or this level's own (a deferred k_claim)
-      const uint64_t dc = c.cand_total - cand_total;
-      cand_total = c.cand_total;
-      if (defer_now_) {              // this level's counters (k_advance) and successor count, for a redo
-        if (!headcopy_) snap_lv_[level % 3] = level;
-        succ_[level % 3] = mat ? cand : dc;
-        succ_lv_[level % 3] = level;
-      }
-      if (dfr) {
-        if (!mat && n) ratio = std::max(1.0, (double)dc / (double)n);
-        cand = 0;
-        prev_gidx = level_gidx;
-        mat = false;
-        if (use_link) {
-          std::swap(link_cur_, link_next_);
-          std::swap(link_cur_cap_, link_next_cap_);
-        }
-        std::swap(pc_cur_, pc_prev_);
-        std::swap(pc_cur_cap_, pc_prev_cap_);
-        pc_valid_ = true;
-      } else {
-        cand = dc;
-      }
-      level_gidx = next_gidx;
-      std::swap(cur_, next_);
-      std::swap(cur_cap_, next_cap_);
-      n = n_new;
-      ++level;
-      if (dfr && capture_level_ == level && n) {
-        KC_TRY(materialize(n, level_gidx, prev_gidx, cand, cand_total));
-        mat = true;
-        KC_TRY(counter_snap(level - 1));
-        captured_.resize(n);
-        KC_HIP_TRY(hipMemcpy(captured_.data(), cur_, n * sizeof(State), hipMemcpyDeviceToHost));
-      }
-      if (n) {
-        if (level > KC_MAX_LEVELS) {
-          set_error("kubecheck: more than %d levels", KC_MAX_LEVELS);
-          return -ENOMEM;
-        }
-        res->level_width[level - 1] = n;
-        res->nlevels = level;
-      }
+      finish(res, 0);
+      return kRunDone;
     }
-    // the last, unexpanded level (max_levels): its states' invariants
-    if (!mat && n) KC_TRY(materialize(n, level_gidx, prev_gidx, cand, cand_total));
-    last_level_ = res->nlevels;
-    last_n_ = n;
-    finish(res, t0, n);
-    if (ablate_) {
-      fprintf(stderr, "kubecheck ablate: claim %.2f ms | successors+LDS %.2f ms | successors only %.2f ms | plan only %.2f ms | settle %.2f | emit %.2f ms"
-              " | emit-no-plan %.2f | emit-no-plan-no-check %.2f | emit-parent-only %.2f"
-              " | successors, XOR fingerprint %.2f | fingerprints, no apply %.2f\n",
-              ktime_ms_[KK_EXPAND], ktime_ms_[KA_LDS], ktime_ms_[KA_COMPUTE], ktime_ms_[KA_PLAN], ktime_ms_[KK_RESOLVE],
-              ktime_ms_[KK_EMIT], ktime_ms_[KA_E1], ktime_ms_[KA_E2], ktime_ms_[KA_E3], ktime_ms_[KA_FPCHEAP],
-              ktime_ms_[KA_NOAPPLY]);
-      KC_HIP_TRY(hipMemcpy(h_ctr_, d_ctr_, sizeof(Counters), hipMemcpyDeviceToHost));
-      fprintf(stderr, "kubecheck claim outcomes (KC_DIAG builds): old %llu lost %llu cur %llu new %llu\n",
-              h_ctr_->claim_out(0), h_ctr_->claim_out(1), h_ctr_->claim_out(2), h_ctr_->claim_out(3));
-      fprintf(stderr, "kubecheck old-state level distance (KC_DIAG): 1:%llu 2:%llu 3:%llu 4:%llu 5-8:%llu 9-16:%llu 17+:%llu\n",
-              h_ctr_->old_dist(0), h_ctr_->old_dist(1), h_ctr_->old_dist(2), h_ctr_->old_dist(3), h_ctr_->old_dist(4),
-              h_ctr_->old_dist(5), h_ctr_->old_dist(6));
-      fprintf(stderr, "kubecheck k_claim successor loop (KC_DIAG): wave trips %llu x 64 lanes, lane trips %llu (%.3f busy);"
-              " dealt by successor count: wave trips %llu (%.3f busy)\n",
-              h_ctr_->loop_max(), h_ctr_->loop_sum(),
-              h_ctr_->loop_max() ? (double)h_ctr_->loop_sum() / (64.0 * h_ctr_->loop_max()) : 0.0,
-              h_ctr_->loop_sorted(),
-              h_ctr_->loop_sorted() ? (double)h_ctr_->loop_sum() / (64.0 * h_ctr_->loop_sorted()) : 0.0);
+    res->distinct += n_new;
+    if (cfg_.verbose)
+      fprintf(stderr, "kubecheck: level %d width %llu -> %llu new, %llu distinct\n",
+              c.level, (unsigned long long)c.n, (unsigned long long)n_new,
+              (unsigned long long)res->distinct);
+    if (!dfr && capture_level_ == c.level + 1 && n_new) {
+      captured_.resize(n_new);
+      KC_HIP_TRY(hipMemcpy(captured_.data(), next_, n_new * sizeof(State), hipMemcpyDeviceToHost));
     }
+    // successors counted this level: the new states' (materialising emit),
+    // or this level's own (a deferred k_claim)
+    const uint64_t dc = h.cand_total - c.cand_total;
+    c.cand_total = h.cand_total;
+    if (defer_now_) {              // this level's counters (k_advance) and successor count, for a redo
+      if (!headcopy_) snap_lv_[c.level % 3] = c.level;
+      succ_[c.level % 3] = c.mat ? c.cand : dc;
+      succ_lv_[c.level % 3] = c.level;
+    }
+    if (dfr) {
+      if (!c.mat && c.n) c.ratio = std::max(1.0, (double)dc / (double)c.n);
+      c.cand = 0;
+      c.prev_gidx = c.level_gidx;
+      c.mat = false;
+      if (lp.use_link) link_cur_.swap(link_next_);
+      pc_cur_.swap(pc_prev_);
+      pc_valid_ = true;
+    } else {
+      c.cand = dc;
+    }
+    c.level_gidx = lp.next_gidx;
+    cur_.swap(next_);
+    c.n = n_new;
+    ++c.level;
+    if (dfr && capture_level_ == c.level && c.n) {
+      KC_TRY(materialize(c));
+      c.mat = true;
+      KC_TRY(counter_snap(c.level - 1));
+      captured_.resize(c.n);
+      KC_HIP_TRY(hipMemcpy(captured_.data(), cur_, c.n * sizeof(State), hipMemcpyDeviceToHost));
+    }
+    return record_level(res, c.level, c.n);
+  }
+
+  // ---- KC_ABLATE=1: cut-down variants of k_claim and k_emit, timed next to
+  // the real launches, and their printout
+  int ablate_claims(uint64_t start, uint64_t cn, unsigned tiles, uint32_t succ_level) {
+    KC_TRY(abl_mask_.grow(cn, st_));
+    timed(KA_LDS, [&] { claim<1>(cur_ + start, cn, start, tiles, succ_level, claim_args_); });
+    timed(KA_COMPUTE, [&] { claim<2>(cur_ + start, cn, start, tiles, succ_level, claim_args_); });
+    timed(KA_PLAN, [&] { claim<3>(cur_ + start, cn, start, tiles, succ_level, claim_args_); });
+    timed(KA_FPCHEAP, [&] { claim<4>(cur_ + start, cn, start, tiles, succ_level, claim_args_); });
+    timed(KA_NOAPPLY, [&] { claim<5>(cur_ + start, cn, start, tiles, succ_level, claim_args_); });
+    return 0;
+  }
+  template <int ABL>
+  void ablate_emit(const LevelCursor& c, const LevelPlan& lp, uint64_t start, uint64_t cn, unsigned grid,
+                   const uint32_t* toff) {
+    hipLaunchKernelGGL((k_emit<M, ABL>), dim3(grid), dim3(256), 0, st_, cur_ + start, cn, start, flags_, newmask_.p,
+                       offsets_.p, next_.p, 0ull, c.level_gidx, lp.next_gidx, tf_.parent(), tf_.ord(), cfg_.keep_trace,
+                       d_ctr_abl_.p, toff);
+  }
+  int ablate_emits(const LevelCursor& c, const LevelPlan& lp, uint64_t start, uint64_t cn, unsigned grid,
+                   const uint32_t* toff) {
+    KC_TRY(d_ctr_abl_.alloc(1));
+    KC_HIP_TRY(hipMemsetAsync(d_ctr_abl_, 0, sizeof(Counters), st_));
+    timed(KA_E1, [&] { ablate_emit<1>(c, lp, start, cn, grid, toff); });
+    timed(KA_E2, [&] { ablate_emit<2>(c, lp, start, cn, grid, toff); });
+    timed(KA_E3, [&] { ablate_emit<3>(c, lp, start, cn, grid, toff); });
+    return 0;
+  }
+  int ablate_report() {
+    fprintf(stderr, "kubecheck ablate: claim %.2f ms | successors+LDS %.2f ms | successors only %.2f ms | plan only %.2f ms | settle %.2f | emit %.2f ms"
+            " | emit-no-plan %.2f | emit-no-plan-no-check %.2f | emit-parent-only %.2f"
+            " | successors, XOR fingerprint %.2f | fingerprints, no apply %.2f\n",
+            ktime_ms_[KK_EXPAND], ktime_ms_[KA_LDS], ktime_ms_[KA_COMPUTE], ktime_ms_[KA_PLAN], ktime_ms_[KK_RESOLVE],
+            ktime_ms_[KK_EMIT], ktime_ms_[KA_E1], ktime_ms_[KA_E2], ktime_ms_[KA_E3], ktime_ms_[KA_FPCHEAP],
+            ktime_ms_[KA_NOAPPLY]);
+    KC_HIP_TRY(hipMemcpy(h_ctr_, d_ctr_, sizeof(Counters), hipMemcpyDeviceToHost));
+    fprintf(stderr, "kubecheck claim outcomes (KC_DIAG builds): old %llu lost %llu cur %llu new %llu\n",
+            h_ctr_->claim_out(0), h_ctr_->claim_out(1), h_ctr_->claim_out(2), h_ctr_->claim_out(3));
+    fprintf(stderr, "kubecheck old-state level distance (KC_DIAG): 1:%llu 2:%llu 3:%llu 4:%llu 5-8:%llu 9-16:%llu 17+:%llu\n",
+            h_ctr_->old_dist(0), h_ctr_->old_dist(1), h_ctr_->old_dist(2), h_ctr_->old_dist(3), h_ctr_->old_dist(4),
+            h_ctr_->old_dist(5), h_ctr_->old_dist(6));
+    fprintf(stderr, "kubecheck k_claim successor loop (KC_DIAG): wave trips %llu x 64 lanes, lane trips %llu (%.3f busy);"
+            " dealt by successor count: wave trips %llu (%.3f busy)\n",
+            h_ctr_->loop_max(), h_ctr_->loop_sum(),
+            h_ctr_->loop_max() ? (double)h_ctr_->loop_sum() / (64.0 * h_ctr_->loop_max()) : 0.0,
+            h_ctr_->loop_sorted(),
+            h_ctr_->loop_sorted() ? (double)h_ctr_->loop_sum() / (64.0 * h_ctr_->loop_sorted()) : 0.0);
     return 0;
   }
 
@@ -777,12 +827,11 @@ class EngineT final : public EngineBase {
     KC_HIP_TRY(hipSetDevice(cfg_.device));
     if (spill_) return check_fps_spill(min_gap, prob);
     const uint64_t cnt = std::max<uint64_t>(cs_.count, 2);
-    unsigned long long *a = nullptr, *b = nullptr, *d_n = nullptr;
-    void* tmp = nullptr;
+    DeviceArray<unsigned long long> a, b, d_n;
+    DeviceArray<uint8_t> tmp;
     int rc = 0;
     unsigned long long n = 0, gap = ~0ull;
-    if (hipMalloc(&a, cnt * 8) != hipSuccess || hipMalloc(&b, cnt * 8) != hipSuccess ||
-        hipMalloc(&d_n, 16) != hipSuccess) {
+    if (a.alloc(cnt) < 0 || b.alloc(cnt) < 0 || d_n.alloc(2) < 0) {
       set_error("kc_engine_check_fps: out of device memory");
       rc = -ENOMEM;
     }
@@ -790,7 +839,7 @@ class EngineT final : public EngineBase {
       (void)hipMemsetAsync(d_n, 0, 8, st_);
       (void)hipMemcpyAsync(d_n + 1, &gap, 8, hipMemcpyHostToDevice, st_);
       hipLaunchKernelGGL(k_claimset_fps, dim3(table_grid(cs_.nslots)), dim3(256), 0, st_,
-                         cs_.words(), cs_.nslots, cs_.word_shift(), a, cnt, d_n);
+                         cs_.words(), cs_.nslots, cs_.word_shift(), a.p, cnt, d_n.p);
       (void)hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, st_);
       if (hipStreamSynchronize(st_) != hipSuccess || n > cnt) {
         set_error("kc_engine_check_fps: fingerprint count %llu > %llu", n, (unsigned long long)cnt);
@@ -799,13 +848,13 @@ class EngineT final : public EngineBase {
     }
     if (!rc && n > 1) {
       size_t tb = 0;
-      if (hipcub::DeviceRadixSort::SortKeys(nullptr, tb, a, b, (int)n, 0, 64, st_) != hipSuccess ||
-          hipMalloc(&tmp, tb) != hipSuccess) {
+      if (hipcub::DeviceRadixSort::SortKeys(nullptr, tb, a.p, b.p, (int)n, 0, 64, st_) != hipSuccess ||
+          tmp.alloc(tb) < 0) {
         set_error("kc_engine_check_fps: sort setup");
         rc = -EIO;
       } else {
-        (void)hipcub::DeviceRadixSort::SortKeys(tmp, tb, a, b, (int)n, 0, 64, st_);
-        hipLaunchKernelGGL(k_adjacent_min_gap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st_, b, n,
+        (void)hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, a.p, b.p, (int)n, 0, 64, st_);
+        hipLaunchKernelGGL(k_adjacent_min_gap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st_, b.p, n,
                            d_n + 1);
         (void)hipMemcpyAsync(&gap, d_n + 1, 8, hipMemcpyDeviceToHost, st_);
         if (hipStreamSynchronize(st_) != hipSuccess) {
@@ -814,8 +863,6 @@ class EngineT final : public EngineBase {
         }
       }
     }
-    for (void* p : {(void*)a, (void*)b, (void*)d_n, tmp})
-      if (p) (void)hipFree(p);
     if (rc) return rc;
     *min_gap = gap;
     *prob = (n > 1 && gap && gap != ~0ull) ? 1.0 / (double)gap : 0.0;
@@ -825,14 +872,14 @@ class EngineT final : public EngineBase {
   // fingerprints: unmixed, merged with the hot table's, sorted)
   int check_fps_spill(uint64_t* min_gap, double* prob) {
     std::vector<uint64_t> keys;
-    KC_TRY(cold_.all_keys(keys));
-    uint64_t* hk = reinterpret_cast<uint64_t*>(sp_arena_);
-    KC_HIP_TRY(hipMemsetAsync(d_spctr_ + 1, 0, 8, st_));
+    KC_TRY(sp_.cold.all_keys(keys));
+    uint64_t* hk = reinterpret_cast<uint64_t*>(sp_.arena.p);
+    KC_HIP_TRY(hipMemsetAsync(sp_.d_spctr + 1, 0, 8, st_));
     hipLaunchKernelGGL(k_claimset_keys, dim3(table_grid(cs_.nslots)), dim3(256), 0, st_, cs_.t,
-                       cs_.nslots, hk, hot_limit_, d_spctr_ + 1);
-    KC_HIP_TRY(hipMemcpyAsync(h_spctr_, d_spctr_, 16, hipMemcpyDeviceToHost, st_));
+                       cs_.nslots, hk, sp_.hot_limit, sp_.d_spctr + 1);
+    KC_HIP_TRY(hipMemcpyAsync(sp_.h_spctr, sp_.d_spctr, 16, hipMemcpyDeviceToHost, st_));
     KC_HIP_TRY(hipStreamSynchronize(st_));
-    const uint64_t c = std::min<uint64_t>(h_spctr_[1], hot_limit_);
+    const uint64_t c = std::min<uint64_t>(sp_.h_spctr[1], sp_.hot_limit);
     const size_t at = keys.size();
     keys.resize(at + c);
     if (c) KC_HIP_TRY(hipMemcpy(keys.data() + at, hk, c * 8, hipMemcpyDeviceToHost));
@@ -962,8 +1009,8 @@ class EngineT final : public EngineBase {
     if (cfg_.trace_host) {
       KC_HIP_TRY(hipStreamSynchronize(st_));
       for (;;) {
-        const unsigned long long p = parent_[g];
-        chain.push_back({g, ord_[g]});
+        const unsigned long long p = tf_.parent()[g];
+        chain.push_back({g, tf_.ord()[g]});
         if (p == ~0ull) break;
         g = p;
         if (chain.size() > KC_MAX_LEVELS + 2) {
@@ -975,9 +1022,9 @@ class EngineT final : public EngineBase {
       // one lane walks the chain in HBM, one readback (instead of two
       // synchronous 8-B copies per level: the time to a counterexample)
       constexpr uint32_t cap = KC_MAX_LEVELS + 3;
-      if (!h_chain_) KC_HIP_TRY(hipHostMalloc(&h_chain_, (cap + 1) * 8));
-      hipLaunchKernelGGL(k_parent_chain, dim3(1), dim3(64), 0, st_, parent_, ord_, (uint64_t)g, h_chain_ + 1, cap,
-                         h_chain_);
+      KC_TRY(h_chain_.alloc(cap + 1));
+      hipLaunchKernelGGL(k_parent_chain, dim3(1), dim3(64), 0, st_, tf_.parent(), tf_.ord(), (uint64_t)g,
+                         h_chain_ + 1, cap, h_chain_.p);
       KC_HIP_TRY(hipGetLastError());
       KC_HIP_TRY(hipStreamSynchronize(st_));
       const uint64_t len = h_chain_[0];
@@ -1002,7 +1049,7 @@ class EngineT final : public EngineBase {
     return 0;
   }
 
-  void finish(kc_result* res, std::chrono::steady_clock::time_point t0, uint64_t left) {
+  void finish(kc_result* res, uint64_t left) {
     // the striped totals are read once, at the end (levels read only the head)
     if (hipMemcpy(h_ctr_, d_ctr_, sizeof(Counters), hipMemcpyDeviceToHost) != hipSuccess)
       set_error("kubecheck: counter readback failed");
@@ -1027,16 +1074,16 @@ class EngineT final : public EngineBase {
     res->narrow_levels = narrow_levels_;
     if (spill_) {
       ColdStats cst;
-      cold_.stats(&cst);
+      sp_.cold.stats(&cst);
       unsigned long long hits = 0;
-      if (hipMemcpy(&hits, d_spctr_, 8, hipMemcpyDeviceToHost) != hipSuccess) set_error("kubecheck: spill counter readback");
-      res->seen_flushes = sp_flushes_;
+      if (hipMemcpy(&hits, sp_.d_spctr, 8, hipMemcpyDeviceToHost) != hipSuccess) set_error("kubecheck: spill counter readback");
+      res->seen_flushes = sp_.flushes;
       res->seen_cold_fps = cst.keys;
-      res->seen_cold_queries = sp_queries_;
+      res->seen_cold_queries = sp_.queries;
       res->seen_cold_hits = hits;
       res->seen_cold_runs = cst.runs;
       res->seen_disk_bytes = cst.disk_written;
-      res->seen_peak_hbm_bytes = cs_.nslots * cs_.slot_bytes() + sp_arena_bytes_ + cst.peak_meta_bytes;
+      res->seen_peak_hbm_bytes = cs_.nslots * cs_.slot_bytes() + sp_.arena.cap + cst.peak_meta_bytes;
       res->seen_filter_tests = cst.filter_tests;
       res->seen_filter_passed = cst.filter_passed;
       res->seen_merges = cst.merges;
@@ -1049,7 +1096,7 @@ class EngineT final : public EngineBase {
                         " checks %.3f), %llu flushes, %llu runs (%llu with %llu keys in HBM), %llu merges, %.1f GB uploaded,"
                         " %llu streaming merge-probes\n",
                 sp_seconds_, sp_flush_seconds_, cst.pin_seconds, cst.merge_seconds, cst.meta_seconds, cst.evict_seconds,
-                sp_check_seconds_, (unsigned long long)sp_flushes_, (unsigned long long)cst.runs,
+                sp_check_seconds_, (unsigned long long)sp_.flushes, (unsigned long long)cst.runs,
                 (unsigned long long)cst.cached_runs, (unsigned long long)cst.cached_keys,
                 (unsigned long long)cst.merges, cst.cache_uploaded / 1e9, (unsigned long long)cst.merge_probes);
     }
@@ -1060,58 +1107,34 @@ class EngineT final : public EngineBase {
       res->frontier_reloaded_bytes = qs.reloaded_bytes;
       res->frontier_peak_hbm_bytes = qs.peak_hbm_bytes;
     }
-    res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0_).count();
   }
 
+  // What is not a buffer.  The buffers free themselves after this, with the
+  // device still current; the stream (st_, declared before them) goes last.
   void release() {
     (void)hipSetDevice(cfg_.device);
     cs_.release();
     q_.reset();
-    if (cfg_.trace_host) {
-      if (parent_) (void)hipHostFree(parent_);
-      if (ord_) (void)hipHostFree(ord_);
-      parent_ = nullptr;
-      ord_ = nullptr;
-    }
-    for (void* p : {(void*)ovf_fp_, (void*)ovf_lk_, (void*)ovf_tile_, (void*)d_ovf_cnt_, (void*)link_cur_,
-                    (void*)link_next_, (void*)pc_cur_, (void*)pc_prev_})
-      if (p) (void)hipFree(p);
-    if (sp_arena_) (void)hipFree(sp_arena_);
-    if (sp_tsum_) (void)hipFree(sp_tsum_);
-    if (d_spctr_) (void)hipFree(d_spctr_);
-    if (h_tsum_) (void)hipHostFree(h_tsum_);
-    if (h_spctr_) (void)hipHostFree(h_spctr_);
-    for (void* p : {(void*)cur_, (void*)next_, (void*)parent_, (void*)ord_, (void*)newmask_, (void*)abl_mask_, (void*)rcount_, (void*)rec_fp_, (void*)rec_lk_,
-                    (void*)offsets_, (void*)scan_tmp_, (void*)d_ctr_, (void*)d_ctr_abl_, (void*)ttot_, (void*)toff_,
-                    (void*)init_fps_, (void*)init_res_, (void*)csum_})
-      if (p) (void)hipFree(p);
-    if (h_ctr_) (void)hipHostFree(h_ctr_);
-    if (h_chain_) (void)hipHostFree(h_chain_);
-    h_chain_ = nullptr;
-    if (h_last_) (void)hipHostFree(h_last_);
-    if (d_ns_) (void)hipFree(d_ns_);
-    if (d_snap_) (void)hipFree(d_snap_);
-    if (d_nsc_) (void)hipFree(d_nsc_);
-    if (d_ntrace_) (void)hipFree(d_ntrace_);
-    if (h_ns_) (void)hipHostFree(h_ns_);
     for (auto& e : ev_pool_) (void)hipEventDestroy(e);
-    if (st_) (void)hipStreamDestroy(st_);
   }
 
   // One launch of k_narrow from the host loop's state; on return the
   // engine's cur_ holds the frontier of level nr.level.
   struct NarrowRun {
-    uint64_t n = 0, level_gidx = 0, cand = 0, new_total = 0, peak = 0;
-    int level = 0, levels = 0, reason = 0;
+    uint64_t new_total = 0, peak = 0;
+    int levels = 0, reason = 0;
   };
-  int run_narrow(uint64_t n, int level, uint64_t level_gidx, uint64_t cand, int stop, NarrowRun& nr) {
+  int run_narrow(LevelCursor& c, int stop, NarrowRun& nr) {
+    const uint64_t n = c.n, level_gidx = c.level_gidx, cand = c.cand;
+    const int level = c.level;
     constexpr uint64_t kBuf = 1ull << 16;            // frontier room (states) of a narrow run
     constexpr uint64_t kNew = 1ull << 20;            // new states one run may add
     const uint64_t bufs = std::max(cand, kBuf);
-    KC_TRY(grow_buffer(cur_, cur_cap_, bufs, true, st_));
-    KC_TRY(grow_buffer(next_, next_cap_, bufs, false, st_));
+    KC_TRY(cur_.grow(bufs, st_, true));
+    KC_TRY(next_.grow(bufs, st_));
     const uint64_t need_par = level_gidx + n + std::max(cand, kNew) + 1;
-    if (cfg_.keep_trace) KC_TRY(grow_trace(need_par, true));
+    if (cfg_.keep_trace) KC_TRY(tf_.grow(cfg_.trace_host, need_par, st_, true));
     KC_TRY(cs_.reserve(std::max(cand, kNew), st_));
     NarrowCtl& h = *h_ns_;
     memset(&h, 0, offsetof(NarrowCtl, widths));
@@ -1120,8 +1143,8 @@ class EngineT final : public EngineBase {
     h.cand = cand;
     h.level = (uint32_t)level;
     h.cur_is_b = 0;
-    h.buf_cap = std::min(cur_cap_, next_cap_);
-    h.par_cap = cfg_.keep_trace ? std::min(par_cap_, ord_cap_) : ~0ull;
+    h.buf_cap = std::min(cur_.cap, next_.cap);
+    h.par_cap = cfg_.keep_trace ? tf_.cap() : ~0ull;
     h.room = cs_.capacity() / 2 > cs_.count ? cs_.capacity() / 2 - cs_.count : 0;
     h.stop_level = (uint32_t)stop;
     h.err[0] = h.err[1] = ~0ull;
@@ -1129,24 +1152,23 @@ class EngineT final : public EngineBase {
     h.reason = narrow_exit_reason(h);
     h.active = h.reason == 0;
     nr = NarrowRun{};
-    if (!h.active) {                             // this level cannot run narrow
-      nr.n = n, nr.level_gidx = level_gidx, nr.cand = cand, nr.level = level, nr.reason = h.reason;
+    if (!h.active) {                             // this level cannot run narrow (c stays)
+      nr.reason = h.reason;
       return 0;
     }
     KC_HIP_TRY(hipMemcpyAsync(d_ns_, h_ns_, offsetof(NarrowCtl, widths), hipMemcpyHostToDevice, st_));
     // both level tables clear (the last level of the previous run left one dirty)
     KC_HIP_TRY(hipMemsetAsync(d_nsc_, 0, sizeof(NarrowScratch), st_));
-    const char* nt = getenv("KC_NARROW_TRACE");
-    if (nt && nt[0] == '1' && !d_ntrace_) KC_HIP_TRY(hipMalloc(&d_ntrace_, kNtraceBytes));
+    if (env_flag("KC_NARROW_TRACE", false)) KC_TRY(d_ntrace_.alloc(kNtraceBytes / 8));
     if (d_ntrace_) KC_HIP_TRY(hipMemsetAsync(d_ntrace_, 0, kNtraceBytes, st_));
     // NARROW_BATCH levels' launches per host sync; they all read the control
     // block, so the ones after the run has ended return at once
-    State *a = cur_, *b = next_;
+    State *a = cur_.p, *b = next_.p;
     uint32_t lev = 0;                            // level launches enqueued in this run
     // the run's first level is expanded on its own; every k_nfinish then
     // expands the states it emits for the level after it
     hipLaunchKernelGGL(k_nexpand<M>, dim3(NARROW_WG * NARROW_SUB), dim3(NARROW_THREADS), 0, st_, a, b, flags_,
-                       cfg_.check_deadlock, 0u, d_ns_, d_nsc_, d_ctr_, d_ntrace_);
+                       cfg_.check_deadlock, 0u, d_ns_.p, d_nsc_.p, d_ctr_.p, d_ntrace_.p);
     for (;;) {
       // (round 6 captured a batch's launches into a hipGraph, replayed with
       // one hipGraphLaunch: Model_1 2.79-2.82 ms against 2.80 — the cost of
@@ -1155,8 +1177,8 @@ class EngineT final : public EngineBase {
       timed(KK_NARROW, [&] {
         for (int k = 0; k < narrow_batch_; ++k, ++lev)
           hipLaunchKernelGGL(k_nfinish<M>, dim3(NARROW_FWG), dim3(NARROW_THREADS), 0, st_, a, b, flags_,
-                             cfg_.check_deadlock, parent_, ord_, cfg_.keep_trace, lev, d_ns_, d_nsc_, cs_.t,
-                             cs_.nslots, d_ctr_, d_ntrace_, cs_.word_shift());
+                             cfg_.check_deadlock, tf_.parent(), tf_.ord(), cfg_.keep_trace, lev, d_ns_.p, d_nsc_.p,
+                             cs_.t, cs_.nslots, d_ctr_.p, d_ntrace_.p, cs_.word_shift());
       });
       KC_HIP_TRY(hipGetLastError());
       KC_HIP_TRY(hipMemcpyAsync(h_ns_, d_ns_, offsetof(NarrowCtl, close_acc), hipMemcpyDeviceToHost, st_));
@@ -1173,23 +1195,20 @@ class EngineT final : public EngineBase {
     KC_HIP_TRY(hipMemcpy(h_ns_->widths + level, d_ns_->widths + level,
                          sizeof(uint64_t) * std::min<uint64_t>(h.levels + 1, KC_MAX_LEVELS - level),
                          hipMemcpyDeviceToHost));
-    nr.n = h.n;
-    nr.level_gidx = h.level_gidx;
-    nr.cand = h.cand;
-    nr.level = (int)h.level;
+    c.n = h.n;
+    c.level_gidx = h.level_gidx;
+    c.cand = h.cand;
+    c.level = (int)h.level;
     nr.levels = (int)h.levels;
     nr.reason = h.reason;
     nr.new_total = h.new_total;
     nr.peak = 0;
-    for (int L = level; L < nr.level && L < KC_MAX_LEVELS; ++L) nr.peak = std::max<uint64_t>(nr.peak, h.widths[L]);
+    for (int L = level; L < c.level && L < KC_MAX_LEVELS; ++L) nr.peak = std::max<uint64_t>(nr.peak, h.widths[L]);
     if (nr.reason == NX_ERROR) h_ctr_->err_key = h.err_key;
     cs_.count += h.new_total;
     narrow_levels_ += h.levels;
     narrow_probes_ += h.probes;
-    if (h.cur_is_b) {
-      std::swap(cur_, next_);
-      std::swap(cur_cap_, next_cap_);
-    }
+    if (h.cur_is_b) cur_.swap(next_);
     return 0;
   }
 
@@ -1198,13 +1217,13 @@ class EngineT final : public EngineBase {
   // are in next_; the states go to cur_.
   DeferArgs defer_args(uint64_t level_gidx, uint64_t prev_gidx) const {
     DeferArgs df;
-    df.prev = next_;
-    df.out = cur_;
+    df.prev = next_.p;
+    df.out = cur_.p;
     if (!cfg_.keep_trace || cfg_.trace_host) {
       df.link = link_cur_;
     } else {
-      df.parent = parent_;
-      df.ord = ord_;
+      df.parent = tf_.parent();
+      df.ord = tf_.ord();
       df.gidx0 = level_gidx;
       df.prev_gidx0 = prev_gidx;
     }
@@ -1213,18 +1232,19 @@ class EngineT final : public EngineBase {
   }
   // Materialise a deferred frontier of n states into cur_ (k_materialize):
   // invariants checked (a violation -> kDeferRetry), actions counted, and
-  // the exact successor count of the level into cand.
-  int materialize(uint64_t n, uint64_t level_gidx, uint64_t prev_gidx, uint64_t& cand, uint64_t& cand_total) {
-    KC_TRY(grow_buffer(cur_, cur_cap_, n, false, st_));
-    const DeferArgs df = defer_args(level_gidx, prev_gidx);
-    hipLaunchKernelGGL(k_materialize<M>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st_, df, n, flags_, d_ctr_);
+  // the exact successor count of the level into c.cand.
+  int materialize(LevelCursor& c) {
+    KC_TRY(cur_.grow(c.n, st_));
+    const DeferArgs df = defer_args(c.level_gidx, c.prev_gidx);
+    hipLaunchKernelGGL(k_materialize<M>, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, st_, df, c.n, flags_,
+                       d_ctr_.p);
     KC_HIP_TRY(hipGetLastError());
     KC_HIP_TRY(hipMemcpyAsync(h_ctr_, d_ctr_, sizeof(Counters), hipMemcpyDeviceToHost, st_));
     KC_HIP_TRY(hipStreamSynchronize(st_));
     if (h_ctr_->defer_flags) return kDeferRetry;
     const uint64_t tot = h_ctr_->next_cand();
-    cand = tot - cand_total;
-    cand_total = tot;
+    c.cand = tot - c.cand_total;
+    c.cand_total = tot;
     return 0;
   }
 
@@ -1233,39 +1253,35 @@ class EngineT final : public EngineBase {
   // the peak of the candidate buffers (verbose: per level).
   int cand_overflow(uint64_t bound, int level, uint64_t n) {
     bound = std::max<uint64_t>(bound, 1);
-    KC_TRY(grow_buffer_tight(ovf_fp_, ovf_fp_cap_, bound, st_));
-    KC_TRY(grow_buffer_tight(ovf_lk_, ovf_lk_cap_, bound, st_));
-    KC_TRY(grow_buffer_tight(ovf_tile_, ovf_tile_cap_, bound, st_));
+    KC_TRY(ovf_fp_.grow_tight(bound, st_));
+    KC_TRY(ovf_lk_.grow_tight(bound, st_));
+    KC_TRY(ovf_tile_.grow_tight(bound, st_));
     // empty when allocated and at every run's start (run(); a run that
     // stopped mid-level may have left entries); k_advance empties it again
     // after every chunk, so a level needs no reset launch of its own
     if (!d_ovf_cnt_) {
-      KC_HIP_TRY(hipMalloc(&d_ovf_cnt_, 8));
+      KC_TRY(d_ovf_cnt_.alloc(1));
       KC_HIP_TRY(hipMemsetAsync(d_ovf_cnt_, 0, 8, st_));
     }
     claim_args_.ovf = CandOvf{d_ovf_cnt_, ovf_fp_, ovf_lk_, ovf_tile_,
-                              std::min(ovf_fp_cap_, std::min(ovf_lk_cap_, ovf_tile_cap_))};
-    const uint64_t b = rcount_cap_ * 4 + rec_fp_cap_ * 8 + rec_lk_cap_ * 4 + ovf_fp_cap_ * 8 + ovf_lk_cap_ * 4 +
-                       ovf_tile_cap_ * 4;
+                              std::min(ovf_fp_.cap, std::min(ovf_lk_.cap, ovf_tile_.cap))};
+    const uint64_t b = rcount_.cap * 4 + rec_fp_.cap * 8 + rec_lk_.cap * 4 + ovf_fp_.cap * 8 + ovf_lk_.cap * 4 +
+                       ovf_tile_.cap * 4;
     cand_buf_peak_ = std::max(cand_buf_peak_, b);
     if (cfg_.verbose)
       fprintf(stderr, "kubecheck: level %d width %llu: candidate buffers %.1f MiB (%.1f B per parent)\n", level,
               (unsigned long long)n, b / 1048576.0, n ? (double)b / (double)n : 0.0);
     return 0;
   }
-  unsigned long long* ovf_fp_ = nullptr;
-  unsigned int *ovf_lk_ = nullptr, *ovf_tile_ = nullptr;
-  uint64_t ovf_fp_cap_ = 0, ovf_lk_cap_ = 0, ovf_tile_cap_ = 0, cand_buf_peak_ = 0;
-  unsigned long long* d_ovf_cnt_ = nullptr;
+  DeviceArray<unsigned long long> ovf_fp_;
+  DeviceArray<unsigned int> ovf_lk_, ovf_tile_;
+  uint64_t cand_buf_peak_ = 0;
+  DeviceArray<unsigned long long> d_ovf_cnt_;
   // deferred frontier (DeferArgs): links of the level being expanded / being
   // emitted, when they are not the (device) trace
-  unsigned long long* link_cur_ = nullptr;
-  unsigned long long* link_next_ = nullptr;
-  uint64_t link_cur_cap_ = 0, link_next_cap_ = 0;
+  DeviceArray<unsigned long long> link_cur_, link_next_;
   // plans (Plan::counts) of the frontier being expanded / of the previous one
-  unsigned long long* pc_cur_ = nullptr;
-  unsigned long long* pc_prev_ = nullptr;
-  uint64_t pc_cur_cap_ = 0, pc_prev_cap_ = 0;
+  DeviceArray<unsigned long long> pc_cur_, pc_prev_;
   bool pc_valid_ = false;
   static constexpr int kDeferRetry = -100000;
   bool defer_ = false, defer_now_ = false;
@@ -1275,14 +1291,11 @@ class EngineT final : public EngineBase {
   // counters as the level left them (k_advance), the host state as it began
   // and its states' successor count
   struct HostSnap {
-    int level = -1;
-    uint64_t n = 0, level_gidx = 0, cand = 0, prev_gidx = 0, cs_count = 0, distinct = 0, peak = 0, cand_total = 0,
-             nslots = 0;
+    LevelCursor c;                      // (c.level = -1: none)
+    uint64_t cs_count = 0, distinct = 0, peak = 0, nslots = 0;
     int nlevels = 0;
-    bool mat = true;
-    double ratio = 1.0;
   };
-  Counters* d_snap_ = nullptr;        // [3]
+  DeviceArray<Counters> d_snap_;      // [3]
   int snap_lv_[3] = {-1, -1, -1};
   HostSnap hs_[3];
   uint64_t succ_[3] = {0, 0, 0};
@@ -1300,7 +1313,9 @@ class EngineT final : public EngineBase {
   // rebuild), level L's claims of level L + 1 dropped from the ClaimSet, L - 1
   // levels expanded; the trace is the path to the state through the parent
   // pointers.  1: not possible here (the caller redoes from L - 1).
-  int report_deferred_invariant(kc_result* res, int L, uint64_t level_gidx, uint64_t n) {
+  int report_deferred_invariant(kc_result* res, const LevelCursor& c) {
+    const int L = c.level;
+    const uint64_t level_gidx = c.level_gidx, n = c.n;
     if (!cfg_.keep_trace || headcopy_ || !d_snap_ || L < 2 || snap_lv_[(L - 1) % 3] != L - 1) return 1;
     // (k_advance copied it with the level head and reset it)
     const unsigned long long inv_n = h_ctr_->defer_inv_n;
@@ -1312,7 +1327,7 @@ class EngineT final : public EngineBase {
       return -EIO;
     }
     KC_TRY(counter_snap(L));
-    hipLaunchKernelGGL(k_counters_restore, dim3(1), dim3(64), 0, st_, d_ctr_, d_snap_[(L - 1) % 3].s,
+    hipLaunchKernelGGL(k_counters_restore, dim3(1), dim3(64), 0, st_, d_ctr_.p, d_snap_[(L - 1) % 3].s,
                        d_snap_[L % 3].s);
     // (first-claim mode writes no claim words: there is no level to drop by,
     // and a drop keyed on the empty word would clear every wide-level entry;
@@ -1337,7 +1352,7 @@ class EngineT final : public EngineBase {
   // The counters after level `lv` (end of a narrow run, or the start) into
   // snapshot lv mod 3.
   int counter_snap(int lv) {
-    if (!d_snap_) KC_HIP_TRY(hipMalloc(&d_snap_, 3 * sizeof(Counters)));
+    KC_TRY(d_snap_.alloc(3));
     KC_HIP_TRY(hipMemcpyAsync(d_snap_[lv % 3].s, d_ctr_->s, sizeof(d_ctr_->s), hipMemcpyDeviceToDevice, st_));
     snap_lv_[lv % 3] = lv;
     return 0;
@@ -1348,36 +1363,33 @@ class EngineT final : public EngineBase {
   // states are cur_ (X = L: k_claim rebuilt or had them) or next_ (X = L -
   // 1: the previous frontier).  Levels <= L then run exactly.  False: not
   // possible exactly (the caller redoes the run from Init).
-  bool redo_from(int X, int L, bool mat, uint64_t dc_here, kc_result* res, uint64_t& n, uint64_t& level_gidx,
-                 uint64_t& cand, uint64_t& prev_gidx, uint64_t& cand_total, double& ratio) {
-    if (!redo_on_ || X < 1 || !d_snap_ || snap_lv_[(X - 1) % 3] != X - 1 || hs_[X % 3].level != X) return false;
+  // On success c is level X's start, materialised.
+  bool redo_from(int X, uint64_t dc_here, kc_result* res, LevelCursor& c) {
+    const int L = c.level;
+    const bool mat = c.mat;
+    if (!redo_on_ || X < 1 || !d_snap_ || snap_lv_[(X - 1) % 3] != X - 1 || hs_[X % 3].c.level != X) return false;
     // level X's own snapshot: X = L - 1 completed; X = L's k_advance wrote it (the anomaly is seen after)
     if (X != L && snap_lv_[X % 3] != X) return false;
     if (X == L && headcopy_) return false;
     const HostSnap& h = hs_[X % 3];
     if (h.nslots != cs_.nslots) return false;      // rehashed since: dropping entries would break probe chains
-    uint64_t c;
+    uint64_t succ;
     if (X == L) {
-      c = mat ? cand : dc_here;                    // k_claim rebuilt the states into cur_ and counted them
+      succ = mat ? c.cand : dc_here;               // k_claim rebuilt the states into cur_ and counted them
     } else {
       if (mat || succ_lv_[X % 3] != X) return false;   // (X's states are the previous frontier, next_)
-      c = succ_[X % 3];
+      succ = succ_[X % 3];
     }
     const unsigned grid = (unsigned)std::min<uint64_t>(8192, (cs_.nslots + 255) / 256);
     hipLaunchKernelGGL(k_claimset_drop, dim3(grid), dim3(256), 0, st_, cs_.t, cs_.nslots, (uint32_t)X + 1);
-    hipLaunchKernelGGL(k_counters_restore, dim3(1), dim3(64), 0, st_, d_ctr_, d_snap_[(X - 1) % 3].s, d_snap_[X % 3].s);
-    hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_);
+    hipLaunchKernelGGL(k_counters_restore, dim3(1), dim3(64), 0, st_, d_ctr_.p, d_snap_[(X - 1) % 3].s,
+                       d_snap_[X % 3].s);
+    hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_.p);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st_) != hipSuccess) return false;
-    if (X != L) {
-      std::swap(cur_, next_);
-      std::swap(cur_cap_, next_cap_);
-    }
-    n = h.n;
-    level_gidx = h.level_gidx;
-    cand = c;
-    prev_gidx = h.prev_gidx;
-    cand_total = h.cand_total;
-    ratio = h.ratio;
+    if (X != L) cur_.swap(next_);
+    c = h.c;                       // (level X, as it began)
+    c.cand = succ;
+    c.mat = true;
     cs_.count = h.cs_count;
     res->distinct = h.distinct;
     res->peak_frontier = h.peak;
@@ -1389,77 +1401,36 @@ class EngineT final : public EngineBase {
     return true;
   }
 
-  // ---- seen-set spill (cfg.seen_hbm_bytes > 0; engine_spill.h, coldset.h).
-  // HBM budget B: the hot ClaimSet takes the largest power-of-two table of
-  // <= B/2 bytes and holds <= 1/2 load (hot_limit_); one scratch arena serves
-  // the flush (the hot keys; the sort borrows the cleared-to-be table) and
-  // the per-chunk queries (keys, locations, found flags, sort space; at most
-  // q_max_ per chunk); the rest is the cold runs' directories and filters.
+  // ---- seen-set spill (cfg.seen_hbm_bytes > 0; the tier is SeenSpill,
+  // engine_spill.h).  The engine's part: the flush never finds more than
+  // hot_limit keys, a chunk's cold check takes every winner at once (q_max
+  // bounds the chunk: spill_cut), and a location is 32 bits.
   int spill_setup() {
-    if (!cs_.t) {
-      const uint64_t B = cfg_.seen_hbm_bytes;
-      // the hot table's share of the budget: 1/2 (round 4 A/B: 1/4 leaves room
-      // for HBM copies of the newest cold runs but doubles the flushes,
-      // 6.0-6.6 s against 4.7-5.3 s on NP=2 at 4 GiB)
-      uint64_t ns = 1ull << 12;
-      while (ns * 2 * sizeof(ClaimEntry) <= B / 2) ns *= 2;
-      KC_TRY(cs_.init(ns, st_));
-      hot_limit_ = ns / 2;
-      q_max_ = std::max<uint64_t>(CLAIM_TILE * 32, hot_limit_ / 3) / 256 * 256;
-      size_t tmp = 0;
-      {
-        hipcub::DoubleBuffer<uint64_t> k(nullptr, nullptr);
-        hipcub::DoubleBuffer<uint32_t> v(nullptr, nullptr);
-        KC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, k, v, (int)q_max_, 0, 64, st_));
-      }
-      sp_qtmp_bytes_ = tmp;
-      const uint64_t qbytes = q_max_ * (8 + 8 + 4 + 4 + 1) + tmp + 1024;
-      sp_arena_bytes_ = std::max<uint64_t>(hot_limit_ * 8, qbytes);
-      KC_HIP_TRY(hipMalloc(&sp_arena_, sp_arena_bytes_));
-      KC_HIP_TRY(hipMalloc(&d_spctr_, 64));
-      KC_HIP_TRY(hipHostMalloc(&h_spctr_, 64));
-      const uint64_t used = ns * sizeof(ClaimEntry) + sp_arena_bytes_;
-      if (used + (1ull << 20) > B) {
-        set_error("kubecheck: seen_hbm_bytes %llu too small (hot table + scratch need %llu B)",
-                  (unsigned long long)B, (unsigned long long)used);
-        return -EINVAL;
-      }
-      ColdSet::Config cc;
-      cc.device = cfg_.device;
-      cc.meta_hbm_bytes = B - used;
-      cc.host_bytes = cfg_.seen_host_bytes;
-      cc.dir = cfg_.spill_dir ? cfg_.spill_dir : "";
-      const char* wk = getenv("KC_COLD_WINDOW");      // disk-run staging window (keys); tests shrink it
-      if (wk && atoll(wk) > 0) cc.window_keys = (uint64_t)atoll(wk);
-      const char* bb = getenv("KC_COLD_BLOOM_BITS");  // filter bits per key (0 = no filters; A/B)
-      if (bb) cc.bloom_bits = atoi(bb);
-      const char* ck = getenv("KC_COLD_CACHE");       // KC_COLD_CACHE=0: no HBM copies of run keys (A/B)
-      cc.cache_keys = !(ck && ck[0] == '0');
-      KC_TRY(cold_.init(cc));
-    } else {
-      KC_TRY(cs_.clear(st_));
-    }
-    cold_.clear();
+    typename SeenSpill<uint32_t>::Policy pol;
+    const uint64_t hot_limit = SeenSpill<uint32_t>::hot_slots(cfg_.seen_hbm_bytes) / 2;
+    pol.flush_cap = hot_limit;
+    pol.q_max = std::max<uint64_t>(CLAIM_TILE * 32, hot_limit / 3) / 256 * 256;
+    pol.who = "kubecheck";
+    pol.dir = cfg_.spill_dir ? cfg_.spill_dir : "";
+    KC_TRY(sp_.setup(cfg_, cs_, st_, pol));
     hot_count_ = 0;
-    sp_flushes_ = sp_queries_ = 0;
     sp_seconds_ = sp_flush_seconds_ = sp_check_seconds_ = 0;
-    const char* ss = getenv("KC_SPILL_SYNC");
-    sp_sync_check_ = ss && ss[0] == '1';
-    KC_HIP_TRY(hipMemsetAsync(d_spctr_, 0, 64, st_));
+    sp_sync_check_ = env_flag("KC_SPILL_SYNC", false);
     return 0;
   }
 
   // Cut [cur, cur + len) to a chunk whose successors (an upper bound on its
-  // hot-table insertions) fit both the table's room and q_max_; flush the
+  // hot-table insertions) fit both the table's room and q_max; flush the
   // hot table into the cold tier first when the room alone would make the
-  // chunk less than half as long as q_max_ allows.
+  // chunk less than half as long as q_max allows.
   int spill_cut(const State* cur, uint64_t len, uint64_t* cut) {
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t plan_len = std::min<uint64_t>(len, std::max<uint64_t>(CLAIM_TILE, q_max_ / 2 / 256 * 256));
+    const uint64_t q_max = sp_.q_max, hot_limit = sp_.hot_limit;
+    const uint64_t plan_len = std::min<uint64_t>(len, std::max<uint64_t>(CLAIM_TILE, q_max / 2 / 256 * 256));
     const uint64_t tiles = (plan_len + 255) / 256;
-    KC_TRY(grow_buffer(sp_tsum_, sp_tsum_cap_, tiles, false, st_));
-    KC_TRY(grow_host_buffer(h_tsum_, h_tsum_cap_, tiles, st_));
-    hipLaunchKernelGGL(k_tile_succ<M>, dim3((unsigned)tiles), dim3(256), 0, st_, cur, plan_len, flags_, sp_tsum_);
+    KC_TRY(sp_tsum_.grow(tiles, st_));
+    KC_TRY(h_tsum_.grow(tiles, st_));
+    hipLaunchKernelGGL(k_tile_succ<M>, dim3((unsigned)tiles), dim3(256), 0, st_, cur, plan_len, flags_, sp_tsum_.p);
     KC_HIP_TRY(hipMemcpyAsync(h_tsum_, sp_tsum_, tiles * 4, hipMemcpyDeviceToHost, st_));
     KC_HIP_TRY(hipStreamSynchronize(st_));
     auto pick = [&](uint64_t cap) {
@@ -1471,15 +1442,15 @@ class EngineT final : public EngineBase {
       }
       return c;
     };
-    const uint64_t room = hot_limit_ > hot_count_ ? hot_limit_ - hot_count_ : 0;
-    uint64_t c = pick(std::min(room, q_max_));
-    if (c < plan_len && c < pick(q_max_) / 2 && hot_count_ > 0) {
+    const uint64_t room = hot_limit > hot_count_ ? hot_limit - hot_count_ : 0;
+    uint64_t c = pick(std::min(room, q_max));
+    if (c < plan_len && c < pick(q_max) / 2 && hot_count_ > 0) {
       KC_TRY(spill_flush());
-      c = pick(q_max_);
+      c = pick(q_max);
     }
     if (c == 0) {
       set_error("kubecheck: a 256-parent tile has %u successors, more than the seen-set's hot table takes per chunk "
-                "(%llu); raise seen_hbm_bytes", h_tsum_[0], (unsigned long long)q_max_);
+                "(%llu); raise seen_hbm_bytes", h_tsum_[0], (unsigned long long)q_max);
       return -ENOMEM;
     }
     *cut = c;
@@ -1490,38 +1461,8 @@ class EngineT final : public EngineBase {
   // Hot table -> one sorted cold run; the table starts over empty.
   int spill_flush() {
     const auto t0 = std::chrono::steady_clock::now();
-    uint64_t* keys = reinterpret_cast<uint64_t*>(sp_arena_);
-    KC_HIP_TRY(hipMemsetAsync(d_spctr_ + 1, 0, 8, st_));
-    hipLaunchKernelGGL(k_claimset_keys, dim3(table_grid(cs_.nslots)), dim3(256), 0, st_, cs_.t,
-                       cs_.nslots, keys, hot_limit_, d_spctr_ + 1);
-    KC_HIP_TRY(hipMemcpyAsync(h_spctr_, d_spctr_, 16, hipMemcpyDeviceToHost, st_));
-    KC_HIP_TRY(hipStreamSynchronize(st_));
-    const uint64_t c = h_spctr_[1];
-    if (c > hot_limit_) {
-      set_error("kubecheck: hot seen-set holds %llu > %llu fingerprints", (unsigned long long)c,
-                (unsigned long long)hot_limit_);
-      return -EIO;
-    }
-    if (c) {
-      // sort in place, borrowing the hot table (cleared right after) as the
-      // alternate buffer and temporary storage
-      uint64_t* alt = reinterpret_cast<uint64_t*>(cs_.t);
-      const uint64_t tab = cs_.nslots * sizeof(ClaimEntry);
-      const uint64_t off = (c * 8 + 255) / 256 * 256;
-      hipcub::DoubleBuffer<uint64_t> kb(keys, alt);
-      size_t tb = 0;
-      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kb, (int)c, 0, 64, st_));
-      if (off + tb > tab) {
-        set_error("kubecheck: seen-set flush sort needs %llu B > %llu", (unsigned long long)(off + tb),
-                  (unsigned long long)tab);
-        return -ENOMEM;
-      }
-      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(reinterpret_cast<uint8_t*>(cs_.t) + off, tb, kb, (int)c, 0, 64, st_));
-      KC_TRY(cold_.add_run(kb.Current(), c, st_));
-    }
-    KC_TRY(cs_.clear(st_));
+    KC_TRY(sp_.flush(cs_, sp_.hot_limit, st_));
     hot_count_ = 0;
-    ++sp_flushes_;
     sp_flush_seconds_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
   }
@@ -1531,34 +1472,29 @@ class EngineT final : public EngineBase {
   // and the tile offsets are recomputed.
   int spill_check(const State* cur, uint64_t cn, unsigned tiles) {
     const auto t0 = std::chrono::steady_clock::now();
-    uint8_t* a = sp_arena_;
-    uint64_t* qk = reinterpret_cast<uint64_t*>(a);
-    uint64_t* qk2 = qk + q_max_;
-    uint32_t* ql = reinterpret_cast<uint32_t*>(qk2 + q_max_);
-    uint32_t* ql2 = ql + q_max_;
-    uint8_t* found = reinterpret_cast<uint8_t*>(ql2 + q_max_);
-    uint8_t* tmp = found + (q_max_ + 255) / 256 * 256;
-    hipLaunchKernelGGL(k_spill_queries<M>, dim3(tiles), dim3(256), 0, st_, cur, cn, flags_, newmask_, toff_, qk, ql);
-    KC_HIP_TRY(hipMemcpyAsync(h_spctr_ + 2, toff_ + tiles, 4, hipMemcpyDeviceToHost, st_));
+    const auto q = sp_.carve();
+    hipLaunchKernelGGL(k_spill_queries<M>, dim3(tiles), dim3(256), 0, st_, cur, cn, flags_, newmask_.p, toff_.p, q.qk,
+                       q.ql);
+    KC_HIP_TRY(hipMemcpyAsync(sp_.h_spctr + 2, toff_ + tiles, 4, hipMemcpyDeviceToHost, st_));
     KC_HIP_TRY(hipStreamSynchronize(st_));
-    const uint64_t m = (uint32_t)h_spctr_[2];
-    if (m > q_max_) {
+    const uint64_t m = (uint32_t)sp_.h_spctr[2];
+    if (m > sp_.q_max) {
       set_error("kubecheck: chunk has %llu new fingerprints > %llu", (unsigned long long)m,
-                (unsigned long long)q_max_);
+                (unsigned long long)sp_.q_max);
       return -EIO;
     }
     hot_count_ += m;
-    sp_queries_ += m;
-    if (m && !cold_.empty()) {
-      hipcub::DoubleBuffer<uint64_t> kb(qk, qk2);
-      hipcub::DoubleBuffer<uint32_t> vb(ql, ql2);
-      size_t tb = sp_qtmp_bytes_;
-      KC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kb, vb, (int)m, 0, 64, st_));
-      KC_HIP_TRY(hipMemsetAsync(found, 0, m, st_));
-      KC_TRY(cold_.probe(kb.Current(), m, found, d_spctr_, st_));
+    sp_.queries += m;
+    if (m && !sp_.cold.empty()) {
+      hipcub::DoubleBuffer<uint64_t> kb(q.qk, q.qk2);
+      hipcub::DoubleBuffer<uint32_t> vb(q.ql, q.ql2);
+      size_t tb = sp_.sp_qtmp_bytes;
+      KC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(q.tmp, tb, kb, vb, (int)m, 0, 64, st_));
+      KC_HIP_TRY(hipMemsetAsync(q.found, 0, m, st_));
+      KC_TRY(sp_.cold.probe(kb.Current(), m, q.found, sp_.d_spctr, st_));
       hipLaunchKernelGGL(k_spill_apply, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st_, kb.Current(),
-                         vb.Current(), found, m, newmask_, ttot_, cs_.t, cs_.nslots, d_ctr_);
-      hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ttot_, tiles, toff_, tscan_reg_);
+                         vb.Current(), q.found, m, newmask_.p, ttot_.p, cs_.t, cs_.nslots, d_ctr_.p);
+      hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ttot_.p, tiles, toff_.p, tscan_reg_);
       KC_HIP_TRY(hipGetLastError());
       if (sp_sync_check_) KC_HIP_TRY(hipStreamSynchronize(st_));   // (KC_SPILL_SYNC=1: time the check itself)
     }
@@ -1569,28 +1505,12 @@ class EngineT final : public EngineBase {
   }
 
   bool spill_ = false;
-  ColdSet cold_;
-  uint64_t hot_limit_ = 0, q_max_ = 0, hot_count_ = 0;
-  uint8_t* sp_arena_ = nullptr;
-  uint64_t sp_arena_bytes_ = 0;
-  size_t sp_qtmp_bytes_ = 0;
-  uint32_t *sp_tsum_ = nullptr, *h_tsum_ = nullptr;
-  uint64_t sp_tsum_cap_ = 0, h_tsum_cap_ = 0;
-  unsigned long long *d_spctr_ = nullptr, *h_spctr_ = nullptr;   // [0] cold hits, [1] flush count
-  uint64_t sp_flushes_ = 0, sp_queries_ = 0;
+  SeenSpill<uint32_t> sp_;
+  uint64_t hot_count_ = 0;            // entries of the hot table
+  DeviceArray<uint32_t> sp_tsum_;
+  PinnedArray<uint32_t> h_tsum_;
   double sp_seconds_ = 0, sp_flush_seconds_ = 0, sp_check_seconds_ = 0;
   bool sp_sync_check_ = false;
-
-  // the trace file (parent index + ordinal per state) in HBM, or in pinned
-  // host RAM with cfg.trace_host (kernels store into it directly)
-  int grow_trace(uint64_t need, bool keep) {
-    if (cfg_.trace_host) {
-      KC_TRY(grow_host_buffer(parent_, par_cap_, need, st_));
-      return grow_host_buffer(ord_, ord_cap_, need, st_);
-    }
-    KC_TRY(grow_buffer(parent_, par_cap_, need, keep, st_));
-    return grow_buffer(ord_, ord_cap_, need, keep, st_);
-  }
 
   // ---- frontiers in the StateQueue (cfg.frontier_hbm_bytes > 0; squeue.h).
   // The queue holds level L's states followed by level L+1's as they are
@@ -1602,8 +1522,7 @@ class EngineT final : public EngineBase {
   // sync that would report an error found among them.  One host sync per
   // chunk: its new-state count sizes the reservation.  Same kernels, same
   // order keys: results equal the in-HBM path's.
-  int run_queued(kc_result* res, std::chrono::steady_clock::time_point t0, uint64_t n, uint64_t cand,
-                 const std::vector<State>& init) {
+  int run_queued(kc_result* res, uint64_t n, uint64_t cand, const std::vector<State>& init) {
     if (!q_) {
       SegQueue::Config qc;
       qc.words = M::W;
@@ -1615,7 +1534,7 @@ class EngineT final : public EngineBase {
       q_.reset(new SegQueue());
       KC_TRY(q_->init(qc));
     }
-    if (!h_last_) KC_HIP_TRY(hipHostMalloc(&h_last_, 16));
+    KC_TRY(h_last_.alloc(4));
     KC_TRY(q_->clear(st_));
     KC_TRY(q_->enqueue_host(reinterpret_cast<const uint64_t*>(init.data()), n, st_));
     const uint64_t chunk = std::min<uint64_t>(
@@ -1623,7 +1542,7 @@ class EngineT final : public EngineBase {
     uint64_t level_gidx = 0, cand_total = 0;
     int level = 1;
     State err_parent{};
-    hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_);
+    hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_.p);
     while (n > 0) {
       if (cfg_.max_levels && level >= cfg_.max_levels) break;
       if (n >= (1ull << 32)) {
@@ -1631,22 +1550,10 @@ class EngineT final : public EngineBase {
         return -ENOMEM;
       }
       const uint64_t next_gidx = level_gidx + n;
-      if (cfg_.keep_trace) KC_TRY(grow_trace(next_gidx + cand + 1, true));
+      if (cfg_.keep_trace) KC_TRY(tf_.grow(cfg_.trace_host, next_gidx + cand + 1, st_, true));
       if (!spill_) KC_TRY(cs_.reserve(cand, st_));
-      const uint64_t cmax = std::min(n, chunk);
-      {
-        const uint64_t tiles = (cmax + CLAIM_TILE - 1) / CLAIM_TILE;
-        KC_TRY(grow_buffer(rcount_, rcount_cap_, tiles, false, st_));
-        if (tscan_) {
-          KC_TRY(grow_buffer(ttot_, ttot_cap_, tiles + 4, false, st_));
-          KC_TRY(grow_buffer(toff_, toff_cap_, tiles + 4, false, st_));
-        }
-        KC_TRY(grow_buffer(rec_fp_, rec_fp_cap_, tiles * CLAIM_RCAP, false, st_));
-        KC_TRY(grow_buffer(rec_lk_, rec_lk_cap_, tiles * CLAIM_RCAP, false, st_));
-        KC_TRY(cand_overflow(cand, level, n));
-      }
-      KC_TRY(grow_buffer(newmask_, mask_cap_, cmax, false, st_));
-      KC_TRY(grow_buffer(offsets_, off_cap_, cmax, false, st_));
+      // (no chunk sums here: first-claim mode is off with the queue)
+      KC_TRY(size_chunk_buffers(std::min(n, chunk), cand, level, n));
       const uint32_t succ_level = (uint32_t)level + 1;
       uint64_t start = 0, level_new = 0, popped = 0, pend = 0;
       unsigned long long seen_err = ~0ull;
@@ -1688,30 +1595,18 @@ class EngineT final : public EngineBase {
         if (spill_) KC_TRY(spill_cut(cur, m, &m));
         ++res->levels_chunks;
         const unsigned tiles = (unsigned)((m + CLAIM_TILE - 1) / CLAIM_TILE);
-        timed(KK_EXPAND, [&] {
-          hipLaunchKernelGGL(k_claim<M>, dim3(tiles), dim3(CLAIM_TILE), 0, st_, cur, m, start, flags_,
-                             cfg_.check_deadlock, cs_.t, cs_.nslots, succ_level, abl_mask_, rcount_, rec_fp_,
-                             rec_lk_, newmask_, d_ctr_, claim_args_);
-        });
-        timed(KK_RESOLVE, [&] { launch_settle(m, start, tiles, succ_level, spill_ ? ttot_ : (uint32_t*)nullptr); });
+        timed(KK_EXPAND, [&] { claim(cur, m, start, tiles, succ_level, claim_args_); });
+        timed(KK_RESOLVE, [&] { launch_settle(m, start, tiles, succ_level, spill_ ? ttot_.p : (uint32_t*)nullptr); });
         if (spill_) {
           // the tile-count path: the cold check clears winners and recounts tiles
           timed(KK_SCAN, [&] {
-            hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ttot_, tiles, toff_, tscan_reg_);
+            hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ttot_.p, tiles, toff_.p, tscan_reg_);
           });
           KC_TRY(spill_check(cur, m, tiles));
           KC_HIP_TRY(hipMemcpyAsync(h_last_, toff_ + tiles, 4, hipMemcpyDeviceToHost, st_));
           h_last_[1] = 0;
         } else {
-          size_t tmp_bytes = 0;
-          const hipcub::TransformInputIterator<uint32_t, NewCount, const uint32_t*> newcnt(newmask_, NewCount());
-          KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, newcnt, offsets_, (int)m, st_));
-          KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-          hipError_t scan_err = hipSuccess;
-          timed(KK_SCAN, [&] {
-            scan_err = hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, newcnt, offsets_, (int)m, st_);
-          });
-          KC_HIP_TRY(scan_err);
+          KC_TRY(scan_newmask(m));
           KC_HIP_TRY(hipMemcpyAsync(h_last_, offsets_ + m - 1, 4, hipMemcpyDeviceToHost, st_));
           KC_HIP_TRY(hipMemcpyAsync(h_last_ + 1, newmask_ + m - 1, 4, hipMemcpyDeviceToHost, st_));
         }
@@ -1724,12 +1619,12 @@ class EngineT final : public EngineBase {
         if (nn) KC_TRY(q_->reserve(nn, &dst, st_));
         timed(KK_EMIT, [&] {
           hipLaunchKernelGGL(k_emit<M>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st_, cur, m, start,
-                             flags_, newmask_, offsets_, reinterpret_cast<State*>(dst), level_new, level_gidx,
-                             next_gidx, parent_, ord_, cfg_.keep_trace, d_ctr_,
-                             spill_ ? (const uint32_t*)toff_ : (const uint32_t*)nullptr);
+                             flags_, newmask_.p, offsets_.p, reinterpret_cast<State*>(dst), level_new, level_gidx,
+                             next_gidx, tf_.parent(), tf_.ord(), cfg_.keep_trace, d_ctr_.p,
+                             spill_ ? (const uint32_t*)toff_.p : (const uint32_t*)nullptr);
         });
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(K_ADVANCE_THREADS), 0, st_, offsets_, newmask_, m, d_ctr_,
-                           spill_ ? (const uint32_t*)toff_ : (const uint32_t*)nullptr, (uint64_t)(spill_ ? tiles : 0),
+        hipLaunchKernelGGL(k_advance, dim3(1), dim3(K_ADVANCE_THREADS), 0, st_, offsets_.p, newmask_.p, m, d_ctr_.p,
+                           spill_ ? (const uint32_t*)toff_.p : (const uint32_t*)nullptr, (uint64_t)(spill_ ? tiles : 0),
                            (unsigned long long*)nullptr, claim_args_.ovf.count);
         KC_HIP_TRY(hipGetLastError());
         if (nn) KC_TRY(q_->commit(nn, st_));
@@ -1749,13 +1644,13 @@ class EngineT final : public EngineBase {
         return -EIO;
       }
       const uint64_t cand_now = h_ctr_->cand_total;
-      hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_);   // next level's head
+      hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_.p);   // next level's head
       cs_.count = spill_ ? hot_count_ : cs_.count + level_new;
       res->peak_frontier = std::max<uint64_t>(res->peak_frontier, n);
       if (seen_err != ~0ull) {
         KC_TRY(report_error(res, seen_err, level, level_gidx, n, have_parent ? &err_parent : nullptr));
         res->distinct += level_new;
-        finish(res, t0, 0);
+        finish(res, 0);
         return 0;
       }
       if (pend) KC_TRY(q_->pop(pend, st_));
@@ -1776,18 +1671,11 @@ class EngineT final : public EngineBase {
       cand = cand_now - cand_total;
       cand_total = cand_now;
       ++level;
-      if (n) {
-        if (level > KC_MAX_LEVELS) {
-          set_error("kubecheck: more than %d levels", KC_MAX_LEVELS);
-          return -ENOMEM;
-        }
-        res->level_width[level - 1] = n;
-        res->nlevels = level;
-      }
+      KC_TRY(record_level(res, level, n));
     }
     last_level_ = res->nlevels;
     last_n_ = n;
-    finish(res, t0, n);
+    finish(res, n);
     return 0;
   }
 
@@ -1845,28 +1733,25 @@ class EngineT final : public EngineBase {
     fputs(a.c_str(), stderr);
     return 0;
   }
-  unsigned long long* d_ntrace_ = nullptr;
+  DeviceArray<unsigned long long> d_ntrace_;
 
   Flags flags_{};
   ShardArgs claim_args_{};
   bool queued_ = false;
   std::unique_ptr<SegQueue> q_;
-  uint32_t* h_last_ = nullptr;       // pinned: a chunk's last offset and mask
-  hipStream_t st_ = nullptr;
-  NarrowCtl *d_ns_ = nullptr, *h_ns_ = nullptr;
-  NarrowScratch* d_nsc_ = nullptr;
+  PinnedArray<uint32_t> h_last_;     // a chunk's last offset and mask
+  DeviceArray<NarrowCtl> d_ns_;
+  PinnedArray<NarrowCtl> h_ns_;
+  DeviceArray<NarrowScratch> d_nsc_;
   bool narrow_on_ = true;
   uint64_t narrow_probes_ = 0;
   uint32_t narrow_epoch_ = 0;
   DevClaimSet cs_;
-  State *cur_ = nullptr, *next_ = nullptr;
-  uint64_t cur_cap_ = 0, next_cap_ = 0;
-  unsigned long long* parent_ = nullptr;
-  uint8_t* ord_ = nullptr;
-  uint64_t par_cap_ = 0, ord_cap_ = 0;
-  uint32_t *newmask_ = nullptr, *offsets_ = nullptr;
-  uint32_t* abl_mask_ = nullptr;
-  Counters* d_ctr_abl_ = nullptr;   // KC_ABLATE: scratch counters of the k_emit variants
+  DeviceArray<State> cur_, next_;
+  TraceFile tf_;                    // in HBM, or in pinned host RAM with cfg.trace_host
+  DeviceArray<uint32_t> newmask_, offsets_;
+  DeviceArray<uint32_t> abl_mask_;
+  DeviceArray<Counters> d_ctr_abl_; // KC_ABLATE: scratch counters of the k_emit variants
   // Default: settle pass B counts each tile's new states and one workgroup
   // scans the tile counts (k_tile_scan); KC_TSCAN=0: the per-parent hipcub
   // scan instead.  KC_HEADCOPY=1: the level head read back by a copy launch
@@ -1882,34 +1767,29 @@ class EngineT final : public EngineBase {
   void launch_settle(uint64_t cn, uint64_t start, unsigned tiles, uint32_t succ_level, uint32_t* ttot,
                      bool ovf_in_scan = false) {
     hipLaunchKernelGGL(k_settle_rec<0>, dim3(tiles + SETTLE_OVF_BLOCKS), dim3(CLAIM_TILE), 0, st_, cn, start,
-                       cs_.t, cs_.nslots, succ_level, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, 0u,
+                       cs_.t, cs_.nslots, succ_level, rcount_.p, rec_fp_.p, rec_lk_.p, newmask_.p, d_ctr_.p, 0u,
                        (uint32_t*)nullptr, tiles, claim_args_.ovf);
     hipLaunchKernelGGL(k_settle_rec<1>, dim3(tiles), dim3(CLAIM_TILE), 0, st_, cn, start, cs_.t, cs_.nslots,
-                       succ_level, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_, 0u, ttot);
+                       succ_level, rcount_.p, rec_fp_.p, rec_lk_.p, newmask_.p, d_ctr_.p, 0u, ttot);
     if (!ovf_in_scan)   // (else k_ovf_tile_scan settles it)
       hipLaunchKernelGGL(k_settle_ovf<1>, dim3(SETTLE_OVF_GRID), dim3(256), 0, st_, claim_args_.ovf, cn, start, cs_.t,
-                         cs_.nslots, succ_level, newmask_, d_ctr_, 0u, ttot);
+                         cs_.nslots, succ_level, newmask_.p, d_ctr_.p, 0u, ttot);
   }
-  // k_chunk_scan's chunk sums (zeroed at allocation and by each scan)
+  // k_chunk_scan's chunk sums (zeroed at allocation, at every run's start
+  // and by each scan)
   bool chunk_scan_ = true;
-  uint32_t* csum_ = nullptr;
-  uint64_t csum_cap_ = 0;
-  uint64_t* init_fps_ = nullptr;
-  int* init_res_ = nullptr;
-  uint64_t init_fps_cap_ = 0, init_res_cap_ = 0;
+  DeviceArray<uint32_t> csum_;
+  DeviceArray<uint64_t> init_fps_;
+  DeviceArray<int> init_res_;
   bool first_claim_ = false;   // KC_FIRST_CLAIM=1: k_claim FIRST, no settle passes (multi-worker TLC semantics)
-  uint32_t *ttot_ = nullptr, *toff_ = nullptr;
-  uint64_t ttot_cap_ = 0, toff_cap_ = 0;
-  unsigned int *rcount_ = nullptr, *rec_lk_ = nullptr;
-  unsigned long long* rec_fp_ = nullptr;
-  uint64_t rcount_cap_ = 0, rec_fp_cap_ = 0, rec_lk_cap_ = 0;
-  uint64_t abl_cap_ = 0;
-  uint64_t mask_cap_ = 0, off_cap_ = 0;
-  uint8_t* scan_tmp_ = nullptr;
-  uint64_t scan_cap_ = 0;
-  Counters* d_ctr_ = nullptr;
-  Counters* h_ctr_ = nullptr;
-  uint64_t* h_chain_ = nullptr;        // pinned: [0] length, then the parent chain (k_parent_chain)
+  DeviceArray<uint32_t> ttot_, toff_;
+  DeviceArray<unsigned int> rcount_, rec_lk_;
+  DeviceArray<unsigned long long> rec_fp_;
+  DeviceArray<uint8_t> scan_tmp_;
+  DeviceArray<Counters> d_ctr_;
+  PinnedArray<Counters> h_ctr_;
+  PinnedArray<uint64_t> h_chain_;      // [0] length, then the parent chain (k_parent_chain)
+  std::chrono::steady_clock::time_point t0_;   // the run's start
   std::vector<hipEvent_t> ev_pool_;
   std::vector<int> ev_kind_;
   size_t ev_used_ = 0;

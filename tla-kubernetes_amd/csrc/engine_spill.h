@@ -1,5 +1,6 @@
 // engine_spill.h — kernels of the engine's seen-set spill mode
-// (kc_model_config.seen_hbm_bytes > 0; coldset.h has the cold tier).
+// (kc_model_config.seen_hbm_bytes > 0; coldset.h has the cold tier), and the
+// tier's host side, SeenSpill, which the sharded stages share (at the end).
 //
 // The hot tier is the ClaimSet at a fixed size.  Per chunk of parents:
 //   k_tile_succ     successors per 256-parent tile, so the host can cut the
@@ -20,11 +21,17 @@
 // winner over a later chunk's copy, which now finds it in the cold tier.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <stdint.h>
+
+#include <algorithm>
+#include <string>
 
 #include "coldset.h"
 #include "engine_kernels.h"
+#include "engine_util.h"
 #include "fpset_dev.h"
+#include "fpset_host.h"
 
 namespace kc {
 
@@ -161,5 +168,144 @@ static __global__ void k_claimset_keys(const ClaimEntry* __restrict__ t, uint64_
     }
   }
 }
+
+// ---- The hot/cold seen-set tier's host side, shared by the engine and the
+// sharded stages (kc_model_config.seen_hbm_bytes > 0).
+// HBM budget B: the hot ClaimSet takes the largest power-of-two table of
+// <= B/2 bytes and holds <= 1/2 load (hot_limit); one scratch arena serves
+// the flush (the hot keys; the sort borrows the cleared-to-be table) and the
+// cold check's queries (keys, locations, found flags, sort space; at most
+// q_max at a time); the rest is the cold runs' directories and filters.
+// What the two callers do differently is theirs (when to flush, how a level
+// or chunk is checked) and comes in as values: Policy.  Loc is the type of a
+// query's location (the engine's parent-in-chunk << 5 | t is 32 bits, the
+// shard's 64); as a class template the tier brings its sort kernels only
+// into the units that use it.
+template <class Loc>
+struct SeenSpill {
+  struct Policy {
+    uint64_t flush_cap = 0;     // most keys a flush may find in the hot table
+    uint64_t q_max = 0;         // queries per cold check (a multiple of 256)
+    const char* who = "";       // message prefix
+    std::string dir;            // the disk tier's directory
+  };
+  struct Queries {
+    uint64_t *qk, *qk2;
+    Loc *ql, *ql2;
+    uint8_t *found, *tmp;
+  };
+
+  DeviceArray<uint8_t> arena;                 // (cap = bytes)
+  DeviceArray<unsigned long long> d_spctr;    // [0] cold hits, [1] flush count
+  PinnedArray<unsigned long long> h_spctr;    // [2] is the caller's (its query count)
+  size_t sp_qtmp_bytes = 0;
+  ColdSet cold;
+  uint64_t hot_limit = 0, q_max = 0;
+  uint64_t flushes = 0, queries = 0;
+  const char* who = "";
+
+  // slots of the hot table for budget B
+  static uint64_t hot_slots(uint64_t B) {
+    // the hot table's share of the budget: 1/2 (round 4 A/B: 1/4 leaves room
+    // for HBM copies of the newest cold runs but doubles the flushes,
+    // 6.0-6.6 s against 4.7-5.3 s on NP=2 at 4 GiB)
+    uint64_t ns = 1ull << 12;
+    while (ns * 2 * sizeof(ClaimEntry) <= B / 2) ns *= 2;
+    return ns;
+  }
+
+  // First run: the table, the arena and the cold tier; every run: all empty.
+  int setup(const kc_model_config& cfg, DevClaimSet& cs, hipStream_t st, const Policy& pol) {
+    if (!cs.t) {
+      const uint64_t B = cfg.seen_hbm_bytes;
+      const uint64_t ns = hot_slots(B);
+      KC_TRY(cs.init(ns, st));
+      hot_limit = ns / 2;
+      q_max = pol.q_max;
+      who = pol.who;
+      size_t tmp = 0;
+      {
+        hipcub::DoubleBuffer<uint64_t> k(nullptr, nullptr);
+        hipcub::DoubleBuffer<Loc> v(nullptr, nullptr);
+        KC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, k, v, (int)q_max, 0, 64, st));
+      }
+      sp_qtmp_bytes = tmp;
+      const uint64_t qbytes = q_max * (8 + 8 + 2 * sizeof(Loc) + 1) + tmp + 1024;
+      KC_TRY(arena.alloc(std::max<uint64_t>(pol.flush_cap * 8, qbytes)));
+      KC_TRY(d_spctr.alloc(8));
+      KC_TRY(h_spctr.alloc(8));
+      const uint64_t used = ns * sizeof(ClaimEntry) + arena.cap;
+      if (used + (1ull << 20) > B) {
+        set_error("%s: seen_hbm_bytes %llu too small (hot table + scratch need %llu B)", who,
+                  (unsigned long long)B, (unsigned long long)used);
+        return -EINVAL;
+      }
+      ColdSet::Config cc;
+      cc.device = cfg.device;
+      cc.meta_hbm_bytes = B - used;
+      cc.host_bytes = cfg.seen_host_bytes;
+      cc.dir = pol.dir;
+      if (const uint64_t wk = env_u64("KC_COLD_WINDOW")) cc.window_keys = wk;   // disk-run staging window (keys); tests shrink it
+      if (const char* bb = getenv("KC_COLD_BLOOM_BITS")) cc.bloom_bits = atoi(bb);   // filter bits per key (0 = no filters; A/B)
+      cc.cache_keys = env_flag("KC_COLD_CACHE", true);   // KC_COLD_CACHE=0: no HBM copies of run keys (A/B)
+      KC_TRY(cold.init(cc));
+    } else {
+      KC_TRY(cs.clear(st));
+    }
+    cold.clear();
+    flushes = queries = 0;
+    KC_HIP_TRY(hipMemsetAsync(d_spctr, 0, 64, st));
+    return 0;
+  }
+
+  // Hot table -> one sorted cold run; the table starts over empty (the
+  // caller's count of its entries is the caller's to reset).
+  int flush(DevClaimSet& cs, uint64_t cap, hipStream_t st) {
+    uint64_t* keys = reinterpret_cast<uint64_t*>(arena.p);
+    KC_HIP_TRY(hipMemsetAsync(d_spctr + 1, 0, 8, st));
+    hipLaunchKernelGGL(k_claimset_keys, dim3(table_grid(cs.nslots)), dim3(256), 0, st, cs.t, cs.nslots, keys, cap,
+                       d_spctr + 1);
+    KC_HIP_TRY(hipMemcpyAsync(h_spctr, d_spctr, 16, hipMemcpyDeviceToHost, st));
+    KC_HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t c = h_spctr[1];
+    if (c > cap) {
+      set_error("%s: hot seen-set holds %llu > %llu fingerprints", who, (unsigned long long)c,
+                (unsigned long long)cap);
+      return -EIO;
+    }
+    if (c) {
+      // sort in place, borrowing the hot table (cleared right after) as the
+      // alternate buffer and temporary storage
+      uint64_t* alt = reinterpret_cast<uint64_t*>(cs.t);
+      const uint64_t tab = cs.nslots * sizeof(ClaimEntry);
+      const uint64_t off = (c * 8 + 255) / 256 * 256;
+      hipcub::DoubleBuffer<uint64_t> kb(keys, alt);
+      size_t tb = 0;
+      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kb, (int)c, 0, 64, st));
+      if (off + tb > tab) {
+        set_error("%s: seen-set flush sort needs %llu B > %llu", who, (unsigned long long)(off + tb),
+                  (unsigned long long)tab);
+        return -ENOMEM;
+      }
+      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(reinterpret_cast<uint8_t*>(cs.t) + off, tb, kb, (int)c, 0, 64, st));
+      KC_TRY(cold.add_run(kb.Current(), c, st));
+    }
+    KC_TRY(cs.clear(st));
+    ++flushes;
+    return 0;
+  }
+
+  // the arena as a cold check uses it
+  Queries carve() const {
+    Queries q;
+    q.qk = reinterpret_cast<uint64_t*>(arena.p);
+    q.qk2 = q.qk + q_max;
+    q.ql = reinterpret_cast<Loc*>(q.qk2 + q_max);
+    q.ql2 = q.ql + q_max;
+    q.found = reinterpret_cast<uint8_t*>(q.ql2 + q_max);
+    q.tmp = q.found + (q_max + 255) / 256 * 256;
+    return q;
+  }
+};
 
 }  // namespace kc

@@ -557,10 +557,8 @@ struct kc_fpset {
   uint8_t* d_seen = nullptr;
   uint64_t stage_cap = 0;
   unsigned long long* d_stats = nullptr;  // STAT_ROWS rows of [new, full, found, -]
-  uint32_t *part_cnt = nullptr, *part_off = nullptr;   // owner partition scratch
-  uint64_t part_cap = 0, part_off_cap = 0;
-  uint8_t* scan_tmp = nullptr;
-  uint64_t scan_cap = 0;
+  DeviceArray<uint32_t> part_cnt, part_off;   // owner partition scratch
+  DeviceArray<uint8_t> scan_tmp;
   uint8_t* h_small = nullptr;   // pinned: SMALL_MAX fps, SMALL_MAX answers, 2 counts (k_small_round)
   std::mutex mu;
   Combiner comb;
@@ -676,8 +674,9 @@ void kc_fpset_destroy(kc_fpset* s) {
   if (s->d_seen) (void)hipFree(s->d_seen);
   if (s->d_stats) (void)hipFree(s->d_stats);
   if (s->h_small) (void)hipHostFree(s->h_small);
-  for (void* p : {(void*)s->part_cnt, (void*)s->part_off, (void*)s->scan_tmp})
-    if (p) (void)hipFree(p);
+  s->part_cnt.reset();
+  s->part_off.reset();
+  s->scan_tmp.reset();
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -871,14 +870,14 @@ int kc_fpset_partition_dev(kc_fpset* s, const uint64_t* fps_dev, uint64_t n, int
     set_error("kc_fpset_partition_dev: batch too large (< 2^32 fingerprints)");
     return -EINVAL;
   }
-  KC_TRY(grow_buffer(s->part_cnt, s->part_cap, cells + 1, false, st));
-  KC_TRY(grow_buffer(s->part_off, s->part_off_cap, cells + 1, false, st));
+  KC_TRY(s->part_cnt.grow(cells + 1, st));
+  KC_TRY(s->part_off.grow(cells + 1, st));
   hipLaunchKernelGGL(k_part_count, dim3((unsigned)ntiles), dim3(256), 0, st, fps_dev, n, (uint32_t)world,
                      (uint32_t)ntiles, s->part_cnt);
   size_t tmp_bytes = 0;
-  KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, s->part_cnt, s->part_off, (int)cells, st));
-  KC_TRY(grow_buffer(s->scan_tmp, s->scan_cap, tmp_bytes + 16, false, st));
-  KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->scan_tmp, tmp_bytes, s->part_cnt, s->part_off, (int)cells, st));
+  KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, s->part_cnt.p, s->part_off.p, (int)cells, st));
+  KC_TRY(s->scan_tmp.grow(tmp_bytes + 16, st));
+  KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->scan_tmp.p, tmp_bytes, s->part_cnt.p, s->part_off.p, (int)cells, st));
   hipLaunchKernelGGL(k_part_scatter, dim3((unsigned)ntiles), dim3(256), 0, st, fps_dev, n, (uint32_t)world,
                      (uint32_t)ntiles, s->part_off, out_dev);
   KC_HIP_TRY(hipGetLastError());

@@ -4,7 +4,9 @@
 #pragma once
 #include <errno.h>
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <hip/hip_runtime.h>
@@ -13,6 +15,19 @@ namespace kc {
 
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 const char* last_error();
+
+// KC_* switches of the environment.  A switch that is on by default goes off
+// with NAME=0 only; one that is off by default goes on with NAME=1 only.
+inline bool env_flag(const char* name, bool def) {
+  const char* v = getenv(name);
+  return def ? !(v && v[0] == '0') : (v && v[0] == '1');
+}
+// A positive number, or 0 when NAME is unset, not a number or not positive.
+inline uint64_t env_u64(const char* name) {
+  const char* v = getenv(name);
+  const long long x = v ? atoll(v) : 0;
+  return x > 0 ? (uint64_t)x : 0;
+}
 
 }  // namespace kc
 

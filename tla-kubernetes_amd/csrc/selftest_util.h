@@ -1,5 +1,5 @@
 // selftest_util.h — host helpers shared by the test-only device harnesses
-// (spill_selftest.hip, emit_selftest.hip): an owning device buffer, the
+// (spill_selftest.hip, emit_selftest.hip, coldset_selftest.hip): an owning device buffer, the
 // upload of a host array, and the check that packed parents are states a
 // kernel may plan and apply.  Nothing of the product path includes this file.
 #pragma once

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/kubecheck.h"
+#include "claim_launch.h"
 #include "coldset.h"
 #include "engine_kernels.h"
 #include "engine_spill.h"
@@ -929,19 +930,15 @@ class ShardT final : public ShardBase {
     // A/B switches (round 5): KC_STAGE=0 packs every level with k_shard_pack
     // (re-expansion + per-parent owner scan); KC_SHARD_TSCAN=0 positions the
     // winners with per-parent / per-record device scans
-    const char* sg = getenv("KC_STAGE");
-    stage_on_ = !(sg && sg[0] == '0');
-    const char* ts = getenv("KC_SHARD_TSCAN");
-    tcount_ = !(ts && ts[0] == '0');
-    const char* dc = getenv("KC_DEFER_CHECK");     // diagnostic: rebuilt states against materialised ones
-    defer_check_ = dc && dc[0] == '1';
+    stage_on_ = env_flag("KC_STAGE", true);
+    tcount_ = env_flag("KC_SHARD_TSCAN", true);
+    defer_check_ = env_flag("KC_DEFER_CHECK", false);   // diagnostic: rebuilt states against materialised ones
     tlc_ = cfg.tlc_order && world > 1;
     // first-claim mode on the counted levels (k_claim FIRST, k_rec_claim_first;
     // no candidates, no settle passes): the first inserter owns a state, as in
     // a TLC -workers N run
     first_ = cfg.first_claim != 0;
-    const char* ck = getenv("KC_CHUNK_SCAN");
-    ocscan_ = !(ck && ck[0] == '0');
+    ocscan_ = env_flag("KC_CHUNK_SCAN", true);
     // (its ClaimSet holds fp words only, as the engine's in this mode: 8-B
     // slots, half the table to clear; the narrow levels write no claim words)
     cs_.compact = first_;
@@ -973,14 +970,14 @@ class ShardT final : public ShardBase {
       return -EINVAL;
     }
     KC_HIP_TRY(hipSetDevice(cfg_.device));
-    KC_HIP_TRY(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-    KC_HIP_TRY(hipMalloc(&d_ctr_, sizeof(Counters)));
-    KC_HIP_TRY(hipHostMalloc(&h_ctr_, sizeof(Counters)));
-    KC_HIP_TRY(hipHostMalloc(&h_exp_, kCtrHead));
-    KC_HIP_TRY(hipMalloc(&d_owner_base_, 16 * sizeof(uint64_t)));
-    KC_HIP_TRY(hipMalloc(&d_ovf_cnt_, 8));     // (zeroed by k_head_reset every level)
-    KC_HIP_TRY(hipMalloc(&d_stage_cur_, 8));   // (likewise)
-    KC_HIP_TRY(hipHostMalloc(&h_owner_base_, 16 * sizeof(uint64_t)));
+    KC_HIP_TRY(hipStreamCreateWithFlags(&st_.s, hipStreamNonBlocking));
+    KC_TRY(d_ctr_.alloc(1));
+    KC_TRY(h_ctr_.alloc(1));
+    KC_TRY(h_exp_.alloc(1));         // (kCtrHead bytes of it are used)
+    KC_TRY(d_owner_base_.alloc(16));
+    KC_TRY(d_ovf_cnt_.alloc(1));     // (zeroed by k_head_reset every level)
+    KC_TRY(d_stage_cur_.alloc(1));   // (likewise)
+    KC_TRY(h_owner_base_.alloc(16));
     KC_HIP_TRY(hipEventCreate(&ev_[0]));
     KC_HIP_TRY(hipEventCreate(&ev_[1]));
     return 0;
@@ -997,9 +994,9 @@ class ShardT final : public ShardBase {
   }
 
   int set_stream(hipStream_t st) override {
-    if (own_st_ && st_) KC_HIP_TRY(hipStreamDestroy(st_));
-    st_ = st;
-    own_st_ = false;
+    if (st_.own && st_.s) KC_HIP_TRY(hipStreamDestroy(st_.s));
+    st_.s = st;
+    st_.own = false;
     return 0;
   }
 
@@ -1014,6 +1011,9 @@ class ShardT final : public ShardBase {
       KC_TRY(cs_.init(fp_slots, st_));
     }
     KC_HIP_TRY(hipMemsetAsync(d_ctr_, 0, sizeof(Counters), st_));
+    // k_owner_cscan's chunk sums: zero when a level starts (a run that
+    // stopped between k_claim and the scan left them dirty)
+    if (ocsum_) KC_HIP_TRY(hipMemsetAsync(ocsum_, 0, ocsum_.cap * sizeof(uint32_t), st_));
     std::vector<State> mine;
     std::vector<unsigned long long> keys;
     std::vector<uint64_t> fps;
@@ -1047,8 +1047,8 @@ class ShardT final : public ShardBase {
     level_base_.assign(1, 0);
     gen_init_ = n_;
     cand_total_ = 0;
-    KC_TRY(grow_buffer(cur_, cur_cap_, std::max<uint64_t>(n_, 1), false, st_));
-    KC_TRY(grow_buffer(pkeys_, pk_cap_, std::max<uint64_t>(n_, 1), false, st_));
+    KC_TRY(cur_.grow(std::max<uint64_t>(n_, 1), st_));
+    KC_TRY(pkeys_.grow(std::max<uint64_t>(n_, 1), st_));
     if (tlc_) {
       // level 1 in TLC order: Init states are distinct, each at its index
       // (G = k); this rank's in increasing k
@@ -1060,9 +1060,9 @@ class ShardT final : public ShardBase {
         bits[gk >> 5] |= 1u << (gk & 31);
       }
       for (uint64_t w = 1; w < words; ++w) brank[w] = brank[w - 1] + (uint32_t)__builtin_popcount(bits[w - 1]);
-      KC_TRY(grow_buffer(gpos_all_, gp_cap_, pk_cap_, false, st_));
-      KC_TRY(grow_buffer(gbits_cur_, gbits_cur_cap_, words, false, st_));
-      KC_TRY(grow_buffer(grank_cur_, grank_cur_cap_, words, false, st_));
+      KC_TRY(gpos_all_.grow(pkeys_.cap, st_));
+      KC_TRY(gbits_cur_.grow(words, st_));
+      KC_TRY(grank_cur_.grow(words, st_));
       if (n_) KC_HIP_TRY(hipMemcpyAsync(gpos_all_, g.data(), n_ * 4, hipMemcpyHostToDevice, st_));
       KC_HIP_TRY(hipMemcpyAsync(gbits_cur_, bits.data(), words * 4, hipMemcpyHostToDevice, st_));
       KC_HIP_TRY(hipMemcpyAsync(grank_cur_, brank.data(), words * 4, hipMemcpyHostToDevice, st_));
@@ -1071,12 +1071,11 @@ class ShardT final : public ShardBase {
     if (n_) {
       KC_HIP_TRY(hipMemcpyAsync(cur_, mine.data(), n_ * sizeof(State), hipMemcpyHostToDevice, st_));
       KC_HIP_TRY(hipMemcpyAsync(pkeys_, keys.data(), n_ * 8, hipMemcpyHostToDevice, st_));
-      uint64_t* d_fps = nullptr;
-      KC_HIP_TRY(hipMalloc(&d_fps, n_ * 8));
+      DeviceArray<uint64_t> d_fps;
+      KC_TRY(d_fps.alloc(n_));
       KC_HIP_TRY(hipMemcpyAsync(d_fps, fps.data(), n_ * 8, hipMemcpyHostToDevice, st_));
-      launch_claimset_insert_list(d_fps, n_, cs_, 1u, nullptr, st_);
+      launch_claimset_insert_list(d_fps.p, n_, cs_, 1u, nullptr, st_);
       KC_HIP_TRY(hipStreamSynchronize(st_));
-      (void)hipFree(d_fps);
     }
     KC_HIP_TRY(hipStreamSynchronize(st_));
     cs_.count = n_;
@@ -1091,6 +1090,13 @@ class ShardT final : public ShardBase {
     if (!dev_empty_) KC_HIP_TRY(hipStreamSynchronize(st_));
     return expand_done(counts, err_key);
   }
+  // k_claim<M, 0, SH, OWN, TLC, FIRST, C8> over the level's n_ parents
+  template <bool SH, int OWN = SH ? 1 : 0, bool TLC = false, bool FIRST = false, bool C8 = false>
+  void claim(uint64_t tiles, size_t dyn, const ShardArgs& sh, const DeferArgs& df) {
+    launch_claim<M, 0, SH, OWN, TLC, FIRST, C8>(st_, (unsigned)tiles, dyn, cur_, n_, 0, flags_, cfg_.check_deadlock, cs_,
+                                                (uint32_t)level_ + 1,
+                                                ClaimBufs{nullptr, rcount_, rec_fp_, rec_lk_, newmask_, d_ctr_}, sh, df);
+  }
   int expand_dev(uint64_t status_new, uint64_t status_err, bool level1, uint64_t* d_row) override {
     KC_HIP_TRY(hipSetDevice(cfg_.device));
     rebuilt_ = false;
@@ -1104,7 +1110,7 @@ class ShardT final : public ShardBase {
       // nothing to claim; a device row still gets its status words
       if (d_row)
         hipLaunchKernelGGL(k_owner_totals, dim3(1), dim3(64), 0, st_, off_, cnt_, (uint64_t)0, (uint32_t)world_,
-                           d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_),
+                           d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_.p),
                            d_row, status_new, status_err, (int)level1, dev_init_err_);
       dev_empty_ = d_row == nullptr;
       dev_zero_ = true;
@@ -1121,33 +1127,33 @@ class ShardT final : public ShardBase {
       // filled hot slots) go into the fixed hot table; flush it first when
       // they might take it past 1/2 load
       const uint64_t need = std::min<uint64_t>(cand_, (uint64_t)((double)cand_ * sp_ratio_ * 1.25) + 4096);
-      if (cs_.count > 0 && cs_.count + need > hot_limit_) KC_TRY(spill_flush());
+      if (cs_.count > 0 && cs_.count + need > sp_.hot_limit) KC_TRY(spill_flush());
     } else {
       // (a deferred frontier's successor count is an estimate: 16 per parent
       // at least, so even MAXSUCC = 32 cannot fill the table, as the engine)
       KC_TRY(cs_.reserve(cand_est_ ? std::max<uint64_t>(cand_, 16 * n_) : cand_, st_));
     }
     const uint64_t tiles = (n_ + CLAIM_TILE - 1) / CLAIM_TILE;
-    KC_TRY(grow_buffer(rcount_, rcount_cap_, tiles, false, st_));
+    KC_TRY(rcount_.grow(tiles, st_));
     // (first-claim mode has no candidates: no records, no overflow list; its
     // k_claim writes each tile's new-state count, k_win_scan's input)
-    if (first_) KC_TRY(grow_buffer(wtot_, wtot_cap_, tiles + 8, false, st_));
-    if (!first_) KC_TRY(grow_buffer(rec_fp_, rec_fp_cap_, tiles * CLAIM_RCAP, false, st_));
-    if (!first_) KC_TRY(grow_buffer(rec_lk_, rec_lk_cap_, tiles * CLAIM_RCAP, false, st_));
+    if (first_) KC_TRY(wtot_.grow(tiles + 8, st_));
+    if (!first_) KC_TRY(rec_fp_.grow(tiles * CLAIM_RCAP, st_));
+    if (!first_) KC_TRY(rec_lk_.grow(tiles * CLAIM_RCAP, st_));
     // candidates past a tile's segment: one overflow list, bounded by the
     // level's successor count
     if (!first_) {
       // (estimated: at least two per parent; the list holds only the
       // candidates past a tile's first 256, a few percent of the successors)
       const uint64_t bound = cand_est_ ? std::max<uint64_t>(cand_, 2 * n_) : std::max<uint64_t>(cand_, 1);
-      KC_TRY(grow_buffer_tight(ovf_fp_, ovf_fp_cap_, bound, st_));
-      KC_TRY(grow_buffer_tight(ovf_lk_, ovf_lk_cap_, bound, st_));
-      KC_TRY(grow_buffer_tight(ovf_tile_, ovf_tile_cap_, bound, st_));
-      ovf_ = CandOvf{d_ovf_cnt_, ovf_fp_, ovf_lk_, ovf_tile_, std::min(ovf_fp_cap_, std::min(ovf_lk_cap_, ovf_tile_cap_))};
+      KC_TRY(ovf_fp_.grow_tight(bound, st_));
+      KC_TRY(ovf_lk_.grow_tight(bound, st_));
+      KC_TRY(ovf_tile_.grow_tight(bound, st_));
+      ovf_ = CandOvf{d_ovf_cnt_, ovf_fp_, ovf_lk_, ovf_tile_, std::min(ovf_fp_.cap, std::min(ovf_lk_.cap, ovf_tile_.cap))};
     }
-    KC_TRY(grow_buffer(newmask_, mask_cap_, n_, false, st_));
-    KC_TRY(grow_buffer(cnt_, cnt_cap_, n_ * world_, false, st_));
-    KC_TRY(grow_buffer(repmask_, rm_cap_, n_, false, st_));
+    KC_TRY(newmask_.grow(n_, st_));
+    KC_TRY(cnt_.grow(n_ * world_, st_));
+    KC_TRY(repmask_.grow(n_, st_));
     ShardArgs sh;
     sh.world = (uint32_t)world_;
     sh.rank = (uint32_t)rank_;
@@ -1163,21 +1169,21 @@ class ShardT final : public ShardBase {
     if (stage_level_) {
       const uint64_t est = std::min<uint64_t>(std::max<uint64_t>(cand_, 1),
                                               (uint64_t)((double)n_ * rec_ratio_ * 1.5) + 65536);
-      KC_TRY(grow_buffer_tight(stage_, stage_cap_, est, st_));
+      KC_TRY(stage_.grow_tight(est, st_));
       const uint64_t cells = tiles * (uint64_t)world_;
-      KC_TRY(grow_buffer(tcnt_, tcnt_cap_, cells + 8, false, st_));
-      KC_TRY(grow_buffer(toff_, toff_cap_, cells + 8, false, st_));
-      KC_TRY(grow_buffer(stoff_, stoff_cap_, tiles, false, st_));
+      KC_TRY(tcnt_.grow(cells + 8, st_));
+      KC_TRY(toff_.grow(cells + 8, st_));
+      KC_TRY(stoff_.grow(tiles, st_));
       ocscan_level_ = ocscan_;
       if (ocscan_level_) {
-        const uint64_t old = ocsum_cap_;
-        KC_TRY(grow_buffer(ocsum_, ocsum_cap_, (tiles / CSUM_TILES + 1) * (uint64_t)world_ + 8, false, st_));
-        if (ocsum_cap_ != old) KC_HIP_TRY(hipMemsetAsync(ocsum_, 0, ocsum_cap_ * sizeof(uint32_t), st_));
+        const uint64_t old = ocsum_.cap;
+        KC_TRY(ocsum_.grow((tiles / CSUM_TILES + 1) * (uint64_t)world_ + 8, st_));
+        if (ocsum_.cap != old) KC_HIP_TRY(hipMemsetAsync(ocsum_, 0, ocsum_.cap * sizeof(uint32_t), st_));
         sh.ocsum = ocsum_;
       }
       sh.stage = stage_;
       sh.stage_cur = d_stage_cur_;
-      sh.stage_cap = stage_cap_;
+      sh.stage_cap = stage_.cap;
       sh.tcnt = tcnt_;
       sh.stoff = stoff_;
     }
@@ -1187,12 +1193,12 @@ class ShardT final : public ShardBase {
     // the previous frontier (next_) and the last receive buffer
     DeferArgs df;
     if (defer_on_) {
-      KC_TRY(grow_buffer(pc_cur_, pc_cur_cap_, n_, false, st_));
+      KC_TRY(pc_cur_.grow(n_, st_));
       df.counts_out = pc_cur_;
     }
     rebuilt_ = cur_deferred_;
     if (cur_deferred_) {
-      KC_TRY(grow_buffer(cur_, cur_cap_, n_, false, st_));
+      KC_TRY(cur_.grow(n_, st_));
       df.prev = next_;
       df.link = link_cur_;
       df.prev_rec = prev_rec_;
@@ -1208,7 +1214,7 @@ class ShardT final : public ShardBase {
       // and the plans this k_claim keeps)
       gen_snap_ok_ = d_row == nullptr && df.counts_out != nullptr;
       if (defer_check_) {
-        if (!d_dchk_) KC_HIP_TRY(hipMalloc(&d_dchk_, 32));
+        KC_TRY(d_dchk_.alloc(4));
         const unsigned long long init[4] = {0ull, ~0ull, ~0ull, 0ull};
         KC_HIP_TRY(hipMemcpyAsync(d_dchk_, init, 32, hipMemcpyHostToDevice, st_));
         KC_HIP_TRY(hipStreamSynchronize(st_));
@@ -1220,31 +1226,16 @@ class ShardT final : public ShardBase {
       // one rank owns everything: the single-GPU engine's claim kernel (no
       // owner counting; claim keys then carry rank 0, which they do anyway)
       if (first_)
-        hipLaunchKernelGGL((k_claim<M, 0, false, 1, false, true, true>), dim3((unsigned)tiles), dim3(CLAIM_TILE), 0, st_,
-                           cur_, n_, (uint64_t)0, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                           (uint32_t)level_ + 1, (uint32_t*)nullptr, rcount_, rec_fp_, rec_lk_, newmask_,
-                           d_ctr_, sh, df);
+        claim<false, 1, false, true, true>(tiles, 0, sh, df);
       else
-        hipLaunchKernelGGL((k_claim<M, 0, false, 1>), dim3((unsigned)tiles), dim3(CLAIM_TILE), 0, st_,
-                           cur_, n_, (uint64_t)0, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                           (uint32_t)level_ + 1, (uint32_t*)nullptr, rcount_, rec_fp_, rec_lk_, newmask_,
-                           d_ctr_, sh, df);
+        claim<false, 1>(tiles, 0, sh, df);
     } else if (first_) {
-      hipLaunchKernelGGL((k_claim<M, 0, true, 1, false, true, true>), dim3((unsigned)tiles), dim3(CLAIM_TILE), dyn, st_,
-                         cur_, n_, (uint64_t)0, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                         (uint32_t)level_ + 1, (uint32_t*)nullptr, rcount_, rec_fp_, rec_lk_, newmask_,
-                         d_ctr_, sh, df);
+      claim<true, 1, false, true, true>(tiles, dyn, sh, df);
     } else {
       if (tlc_)
-        hipLaunchKernelGGL((k_claim<M, 0, true, 1, true>), dim3((unsigned)tiles), dim3(CLAIM_TILE), dyn, st_,
-                           cur_, n_, (uint64_t)0, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                           (uint32_t)level_ + 1, (uint32_t*)nullptr, rcount_, rec_fp_, rec_lk_, newmask_,
-                           d_ctr_, sh, df);
+        claim<true, 1, true>(tiles, dyn, sh, df);
       else
-        hipLaunchKernelGGL((k_claim<M, 0, true>), dim3((unsigned)tiles), dim3(CLAIM_TILE), dyn, st_,
-                           cur_, n_, (uint64_t)0, flags_, cfg_.check_deadlock, cs_.t, cs_.nslots,
-                           (uint32_t)level_ + 1, (uint32_t*)nullptr, rcount_, rec_fp_, rec_lk_, newmask_,
-                           d_ctr_, sh, df);
+        claim<true>(tiles, dyn, sh, df);
     }
     if (cfg_.timing) KC_HIP_TRY(hipEventRecord(ev_[1], st_));
 #ifdef KC_CLAIM_TRACE
@@ -1273,11 +1264,11 @@ class ShardT final : public ShardBase {
       if (ocscan_level_)
         hipLaunchKernelGGL(k_owner_cscan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ocsum_,
                            (uint32_t)((tiles + CSUM_TILES - 1) / CSUM_TILES), (uint32_t)world_, toff_, d_owner_base_,
-                           d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_), d_row, status_new,
+                           d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_.p), d_row, status_new,
                            status_err, (int)level1, dev_init_err_);
       else
       hipLaunchKernelGGL(k_owner_tscan, dim3(1), dim3(TSCAN_THREADS), 0, st_, tcnt_, (uint32_t)tiles, (uint32_t)world_,
-                         toff_, d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_),
+                         toff_, d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_.p),
                          d_row, status_new, status_err, (int)level1, dev_init_err_);
       KC_HIP_TRY(hipGetLastError());
       return 0;
@@ -1285,7 +1276,7 @@ class ShardT final : public ShardBase {
     // one exclusive scan over the owner-major matrix = every record's position
     // in the owner-grouped send buffer (nothing to send at world 1)
     const uint64_t cells = n_ * (uint64_t)world_;
-    KC_TRY(grow_buffer(off_, off_cap_, cells, false, st_));
+    KC_TRY(off_.grow(cells, st_));
     if (cells >= (1ull << 31)) {
       set_error("kc_shard_expand: frontier x world = %llu cells exceeds one scan (2^31)",
                 (unsigned long long)cells);
@@ -1293,18 +1284,18 @@ class ShardT final : public ShardBase {
     }
     if (world_ > 1 && cells <= OWNER_SMALL_SCAN) {
       hipLaunchKernelGGL(k_owner_scan_small, dim3(1), dim3(1024), 0, st_, cnt_, off_, n_, (uint32_t)world_,
-                         d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_),
+                         d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_.p),
                          d_row, status_new, status_err, (int)level1, dev_init_err_);
     } else {
       if (world_ > 1) {
         size_t tmp_bytes = 0;
         const hipcub::TransformInputIterator<uint32_t, Widen8, const uint8_t*> cnt32(cnt_, Widen8());
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt32, off_, (int)cells, st_));
-        KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, cnt32, off_, (int)cells, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt32, off_.p, (int)cells, st_));
+        KC_TRY(scan_tmp_.grow(tmp_bytes + 16, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_.p, tmp_bytes, cnt32, off_.p, (int)cells, st_));
       }
       hipLaunchKernelGGL(k_owner_totals, dim3(1), dim3(64), 0, st_, off_, cnt_, n_, (uint32_t)world_,
-                         d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_),
+                         d_owner_base_, d_ctr_, h_owner_base_, reinterpret_cast<unsigned long long*>(h_exp_.p),
                          d_row, status_new, status_err, (int)level1, dev_init_err_);
     }
     KC_HIP_TRY(hipGetLastError());
@@ -1435,12 +1426,12 @@ class ShardT final : public ShardBase {
         // (staging overflowed this level: the per-parent owner-major scan
         // that k_shard_pack positions its records with)
         const uint64_t cells = n_ * (uint64_t)world_;
-        KC_TRY(grow_buffer(off_, off_cap_, cells, false, st_));
+        KC_TRY(off_.grow(cells, st_));
         size_t tmp_bytes = 0;
         const hipcub::TransformInputIterator<uint32_t, Widen8, const uint8_t*> cnt32(cnt_, Widen8());
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt32, off_, (int)cells, st_));
-        KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, cnt32, off_, (int)cells, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt32, off_.p, (int)cells, st_));
+        KC_TRY(scan_tmp_.grow(tmp_bytes + 16, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_.p, tmp_bytes, cnt32, off_.p, (int)cells, st_));
       }
       hipLaunchKernelGGL(k_shard_pack<M>, dim3((unsigned)((n_ + 255) / 256)), dim3(256), 0, st_,
                          cur_, n_, flags_, (uint32_t)world_, (uint64_t)rank_, off_, repmask_,
@@ -1449,7 +1440,7 @@ class ShardT final : public ShardBase {
     }
     // else stream-ordered with the caller (set_stream, or the native level
     // loop, which synchronises before it moves the records itself)
-    if (own_st_ && !async_pack_) KC_HIP_TRY(hipStreamSynchronize(st_));
+    if (st_.own && !async_pack_) KC_HIP_TRY(hipStreamSynchronize(st_));
     return 0;
   }
 
@@ -1480,10 +1471,10 @@ class ShardT final : public ShardBase {
       // first-claim mode: the records' CASes (their block counts after this
       // level's own tile counts, which k_claim wrote), one scan, the emit
       const unsigned lt = n_ ? tiles : 0u, rb = n ? rgrid : 0u;
-      KC_TRY(grow_buffer(wtot_, wtot_cap_, (uint64_t)lt + rb + 8, true, st_));
-      KC_TRY(grow_buffer(woff_, woff_cap_, (uint64_t)lt + rb + 8, false, st_));
+      KC_TRY(wtot_.grow((uint64_t)lt + rb + 8, st_, true));
+      KC_TRY(woff_.grow((uint64_t)lt + rb + 8, st_));
       if (n) {
-        KC_TRY(grow_buffer(isnew_, isnew_cap_, n, false, st_));
+        KC_TRY(isnew_.grow(n, st_));
         hipLaunchKernelGGL(k_rec_claim_first<M>, dim3(rgrid), dim3(256), 0, st_, in, n, cs_.t, cs_.nslots, isnew_,
                            wtot_ + lt, d_ctr_, cs_.compact ? 1 : 0);
       }
@@ -1491,10 +1482,10 @@ class ShardT final : public ShardBase {
       return insert_emit(in, n, true, n_new, err_key);
     }
     if (n) {
-      KC_TRY(grow_buffer(rfp_, rfp_cap_, n, false, st_));
-      KC_TRY(grow_buffer(flag_, flag_cap_, n, false, st_));
-      KC_TRY(grow_buffer(isnew_, isnew_cap_, n, false, st_));
-      KC_TRY(grow_buffer(ioff_, ioff_cap_, n, false, st_));
+      KC_TRY(rfp_.grow(n, st_));
+      KC_TRY(flag_.grow(n, st_));
+      KC_TRY(isnew_.grow(n, st_));
+      KC_TRY(ioff_.grow(n, st_));
       hipLaunchKernelGGL(k_rec_claim<M>, dim3(rgrid), dim3(256), 0, st_, in, n, cs_.t, cs_.nslots,
                          succ_level, rfp_, flag_, d_ctr_, (int)tlc_);
     }
@@ -1533,8 +1524,8 @@ class ShardT final : public ShardBase {
     };
     settle(0, ob, (uint32_t*)nullptr);
     if (tc) {
-      KC_TRY(grow_buffer(wtot_, wtot_cap_, (uint64_t)lt + rb + 8, false, st_));
-      KC_TRY(grow_buffer(woff_, woff_cap_, (uint64_t)lt + rb + 8, false, st_));
+      KC_TRY(wtot_.grow((uint64_t)lt + rb + 8, st_));
+      KC_TRY(woff_.grow((uint64_t)lt + rb + 8, st_));
       if (lt + rb) settle(1, 0, wtot_);
       if (n_ && n_ <= FUSE_OVF_SCAN_MAX) {
         hipLaunchKernelGGL(k_ovf_win_scan, dim3(1), dim3(TSCAN_THREADS), 0, st_, ovf_, n_, cs_.t, cs_.nslots,
@@ -1572,18 +1563,18 @@ class ShardT final : public ShardBase {
     emitted_links_ = links;
     last_in_ = in;
     const uint64_t bound = cand_ + n;
-    if (!links || defer_check_) KC_TRY(grow_buffer(next_, next_cap_, std::max<uint64_t>(bound, 1), false, st_));
+    if (!links || defer_check_) KC_TRY(next_.grow(std::max<uint64_t>(bound, 1), st_));
     const uint64_t next_gidx = level_base_.back() + n_;
-    KC_TRY(grow_buffer(pkeys_, pk_cap_, next_gidx + bound + 1, true, st_));
-    if (tlc_) KC_TRY(grow_buffer(gpos_all_, gp_cap_, pk_cap_, true, st_));
-    if (links) KC_TRY(grow_buffer(link_next_, link_next_cap_, std::max<uint64_t>(bound, 1), false, st_));
+    KC_TRY(pkeys_.grow(next_gidx + bound + 1, st_, true));
+    if (tlc_) KC_TRY(gpos_all_.grow(pkeys_.cap, st_, true));
+    if (links) KC_TRY(link_next_.grow(std::max<uint64_t>(bound, 1), st_));
     const unsigned lb = (unsigned)((n_ + 255) / 256), eg = std::max(lb + (n ? rgrid : 0u), 1u);
     const int tail = eg <= SHARD_TAIL_BLOCKS;
     if (links && defer_check_) {
       // (diagnostic) the materialising emit too, into next_ — which the next
       // level's rebuild then compares with — on scratch counters and keys
-      if (!d_ctr_dbg_) KC_HIP_TRY(hipMalloc(&d_ctr_dbg_, sizeof(Counters)));
-      KC_TRY(grow_buffer(pk_dbg_, pk_dbg_cap_, bound + 1, false, st_));
+      KC_TRY(d_ctr_dbg_.alloc(1));
+      KC_TRY(pk_dbg_.grow(bound + 1, st_));
       hipLaunchKernelGGL(k_shard_emit<M>, dim3(eg), dim3(256), 0, st_, cur_, n_, lb, flags_, (uint64_t)rank_, newmask_,
                          offsets_, in, n, isnew_, ioff_, next_, pk_dbg_, (uint64_t)0, d_ctr_dbg_,
                          (unsigned long long*)nullptr, 0, woff_);
@@ -1593,25 +1584,25 @@ class ShardT final : public ShardBase {
         hipLaunchKernelGGL(k_shard_emit_links<M>, dim3(eg), dim3(256), 0, st_, n_, lb, (uint64_t)rank_,
                            tlc_ ? gpos_cur() : (const uint32_t*)nullptr, newmask_, in, n,
                            isnew_, woff_, link_next_, pkeys_, next_gidx,
-                           std::min<uint64_t>(link_next_cap_, pk_cap_ - next_gidx), d_ctr_,
-                           reinterpret_cast<unsigned long long*>(h_ctr_), tail);
+                           std::min<uint64_t>(link_next_.cap, pkeys_.cap - next_gidx), d_ctr_,
+                           reinterpret_cast<unsigned long long*>(h_ctr_.p), tail);
       else
         hipLaunchKernelGGL(k_shard_emit<M>, dim3(eg), dim3(256), 0, st_, cur_, n_, lb, flags_, (uint64_t)rank_,
                            newmask_, offsets_, in, n, isnew_, ioff_, next_, pkeys_, next_gidx, d_ctr_,
-                           reinterpret_cast<unsigned long long*>(h_ctr_), tail,
+                           reinterpret_cast<unsigned long long*>(h_ctr_.p), tail,
                            tc ? woff_ : (const uint32_t*)nullptr);
       if (!tail)
         hipLaunchKernelGGL(k_shard_cand, dim3(1), dim3(64), 0, st_, d_ctr_,
-                           reinterpret_cast<unsigned long long*>(h_ctr_));
+                           reinterpret_cast<unsigned long long*>(h_ctr_.p));
     };
     emit();
     KC_HIP_TRY(hipGetLastError());
     KC_HIP_TRY(hipStreamSynchronize(st_));
     if (links && (h_ctr_->defer_flags & DF_CAPACITY)) {
       const uint64_t need = h_ctr_->level_new;
-      KC_TRY(grow_buffer(link_next_, link_next_cap_, need, false, st_));
-      KC_TRY(grow_buffer(pkeys_, pk_cap_, next_gidx + need + 1, true, st_));
-      if (tlc_) KC_TRY(grow_buffer(gpos_all_, gp_cap_, pk_cap_, true, st_));
+      KC_TRY(link_next_.grow(need, st_));
+      KC_TRY(pkeys_.grow(next_gidx + need + 1, st_, true));
+      if (tlc_) KC_TRY(gpos_all_.grow(pkeys_.cap, st_, true));
       KC_HIP_TRY(hipMemsetAsync(&d_ctr_->defer_flags, 0, 8, st_));
       ++emit_retries_;
       emit();
@@ -1619,7 +1610,7 @@ class ShardT final : public ShardBase {
       KC_HIP_TRY(hipStreamSynchronize(st_));
       if (h_ctr_->defer_flags & DF_CAPACITY) {
         set_error("kc_shard_insert: %llu links do not fit %llu", (unsigned long long)need,
-                  (unsigned long long)link_next_cap_);
+                  (unsigned long long)link_next_.cap);
         return -ENOMEM;
       }
     }
@@ -1656,7 +1647,7 @@ class ShardT final : public ShardBase {
   // Exclusive scans of the own winners' newmask popcounts (offsets_) and the
   // records' isnew flags (ioff_); C->chunk_base / level_new = the totals.
   int scan_winners(uint64_t n) {
-    if (n_) KC_TRY(grow_buffer(offsets_, offsets_cap_, n_, false, st_));
+    if (n_) KC_TRY(offsets_.grow(n_, st_));
     if (n_ <= SHARD_SMALL_SCAN && n <= SHARD_SMALL_SCAN) {
       hipLaunchKernelGGL(k_shard_scan_small, dim3(1), dim3(1024), 0, st_, newmask_, n_, offsets_, isnew_, n, ioff_,
                          d_ctr_);
@@ -1664,116 +1655,46 @@ class ShardT final : public ShardBase {
       size_t tmp_bytes = 0;
       if (n_) {
         const hipcub::TransformInputIterator<uint32_t, NewCount, const uint32_t*> newcnt(newmask_, NewCount());
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, newcnt, offsets_, (int)n_, st_));
-        KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, newcnt, offsets_, (int)n_, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, newcnt, offsets_.p, (int)n_, st_));
+        KC_TRY(scan_tmp_.grow(tmp_bytes + 16, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_.p, tmp_bytes, newcnt, offsets_.p, (int)n_, st_));
       }
       if (n) {
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, isnew_, ioff_, (int)n, st_));
-        KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, isnew_, ioff_, (int)n, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, isnew_.p, ioff_.p, (int)n, st_));
+        KC_TRY(scan_tmp_.grow(tmp_bytes + 16, st_));
+        KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_.p, tmp_bytes, isnew_.p, ioff_.p, (int)n, st_));
       }
       hipLaunchKernelGGL(k_shard_base, dim3(1), dim3(64), 0, st_, offsets_, newmask_, n_, ioff_, isnew_, n, d_ctr_);
     }
     return 0;
   }
 
-  // ---- seen-set spill (cfg.seen_hbm_bytes > 0; the engine's scheme,
-  // engine.hip spill_setup/spill_flush/spill_check, with whole levels: the
-  // sharded level cannot be cut into chunks without cutting every rank's).
-  // Budget B per rank: the hot ClaimSet takes the largest power-of-two table
-  // of <= B/2 bytes, flushed before a level whose claims might take it past
-  // 1/2 load (a level may go on to 7/8: an estimate, not a bound, decides
-  // the flush); one arena serves the flush (up to 7/8 of the slots' keys) and
-  // the level's cold check (q_max_ queries per window); the rest is the cold
-  // runs' directories and filters.
+  // ---- seen-set spill (cfg.seen_hbm_bytes > 0; the tier is SeenSpill,
+  // engine_spill.h, as the engine's), with whole levels: the sharded level
+  // cannot be cut into chunks without cutting every rank's.
+  // Budget B per rank: the hot table is flushed before a level whose claims
+  // might take it past 1/2 load (a level may go on to 7/8, hot_hard_: an
+  // estimate, not a bound, decides the flush); the arena serves the flush
+  // (up to 7/8 of the slots' keys) and the level's cold check (q_max queries
+  // per window, 64-bit locations).
   int spill_setup() {
-    if (!cs_.t) {
-      const uint64_t B = cfg_.seen_hbm_bytes;
-      uint64_t ns = 1ull << 12;
-      while (ns * 2 * sizeof(ClaimEntry) <= B / 2) ns *= 2;
-      KC_TRY(cs_.init(ns, st_));
-      hot_limit_ = ns / 2;
-      hot_hard_ = ns / 8 * 7;
-      uint64_t arena = hot_hard_ * 8;
-      q_max_ = std::max<uint64_t>(256, arena / 48 / 256 * 256);
-      const char* qm = getenv("KC_SEEN_QMAX");        // queries per cold-check window (tests: many windows)
-      if (qm && atoll(qm) >= 256) q_max_ = std::min<uint64_t>(q_max_, (uint64_t)atoll(qm) / 256 * 256);
-      size_t tmp = 0;
-      {
-        hipcub::DoubleBuffer<uint64_t> k(nullptr, nullptr);
-        hipcub::DoubleBuffer<uint64_t> v(nullptr, nullptr);
-        KC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, k, v, (int)q_max_, 0, 64, st_));
-      }
-      sp_qtmp_bytes_ = tmp;
-      arena = std::max<uint64_t>(arena, q_max_ * 33 + tmp + 1024);
-      sp_arena_bytes_ = arena;
-      KC_HIP_TRY(hipMalloc(&sp_arena_, arena));
-      KC_HIP_TRY(hipMalloc(&d_spctr_, 64));
-      KC_HIP_TRY(hipHostMalloc(&h_spctr_, 64));
-      const uint64_t used = ns * sizeof(ClaimEntry) + arena;
-      if (used + (1ull << 20) > B) {
-        set_error("kc_shard: seen_hbm_bytes %llu too small (hot table + scratch need %llu B)",
-                  (unsigned long long)B, (unsigned long long)used);
-        return -EINVAL;
-      }
-      ColdSet::Config cc;
-      cc.device = cfg_.device;
-      cc.meta_hbm_bytes = B - used;
-      cc.host_bytes = cfg_.seen_host_bytes;
-      cc.dir = spill_dir_;
-      const char* wk = getenv("KC_COLD_WINDOW");      // disk-run staging window (keys); tests shrink it
-      if (wk && atoll(wk) > 0) cc.window_keys = (uint64_t)atoll(wk);
-      const char* bb = getenv("KC_COLD_BLOOM_BITS");  // filter bits per key (0 = no filters; A/B)
-      if (bb) cc.bloom_bits = atoi(bb);
-      const char* ck = getenv("KC_COLD_CACHE");       // KC_COLD_CACHE=0: no HBM copies of run keys (A/B)
-      cc.cache_keys = !(ck && ck[0] == '0');
-      KC_TRY(cold_.init(cc));
-    } else {
-      KC_TRY(cs_.clear(st_));
-    }
-    cold_.clear();
-    sp_flushes_ = sp_queries_ = 0;
+    typename SeenSpill<uint64_t>::Policy pol;
+    hot_hard_ = SeenSpill<uint64_t>::hot_slots(cfg_.seen_hbm_bytes) / 8 * 7;
+    pol.flush_cap = hot_hard_;
+    pol.q_max = std::max<uint64_t>(256, hot_hard_ * 8 / 48 / 256 * 256);
+    // KC_SEEN_QMAX: queries per cold-check window (tests: many windows)
+    if (const uint64_t qm = env_u64("KC_SEEN_QMAX"); qm >= 256) pol.q_max = std::min<uint64_t>(pol.q_max, qm / 256 * 256);
+    pol.who = "kc_shard";
+    pol.dir = spill_dir_;
+    KC_TRY(sp_.setup(cfg_, cs_, st_, pol));
     sp_ratio_ = 1.0;
-    KC_HIP_TRY(hipMemsetAsync(d_spctr_, 0, 64, st_));
     return 0;
   }
 
   // Hot table -> one sorted cold run; the table starts over empty.
   int spill_flush() {
-    uint64_t* keys = reinterpret_cast<uint64_t*>(sp_arena_);
-    KC_HIP_TRY(hipMemsetAsync(d_spctr_ + 1, 0, 8, st_));
-    hipLaunchKernelGGL(k_claimset_keys, dim3(table_grid(cs_.nslots)), dim3(256), 0, st_, cs_.t, cs_.nslots, keys,
-                       hot_hard_, d_spctr_ + 1);
-    KC_HIP_TRY(hipMemcpyAsync(h_spctr_, d_spctr_, 16, hipMemcpyDeviceToHost, st_));
-    KC_HIP_TRY(hipStreamSynchronize(st_));
-    const uint64_t c = h_spctr_[1];
-    if (c > hot_hard_) {
-      set_error("kc_shard: hot seen-set holds %llu > %llu fingerprints", (unsigned long long)c,
-                (unsigned long long)hot_hard_);
-      return -EIO;
-    }
-    if (c) {
-      // sorted in place, the hot table (cleared right after) lending the
-      // alternate buffer and the temporary storage
-      uint64_t* alt = reinterpret_cast<uint64_t*>(cs_.t);
-      const uint64_t tab = cs_.nslots * sizeof(ClaimEntry);
-      const uint64_t off = (c * 8 + 255) / 256 * 256;
-      hipcub::DoubleBuffer<uint64_t> kb(keys, alt);
-      size_t tb = 0;
-      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kb, (int)c, 0, 64, st_));
-      if (off + tb > tab) {
-        set_error("kc_shard: seen-set flush sort needs %llu B > %llu", (unsigned long long)(off + tb),
-                  (unsigned long long)tab);
-        return -ENOMEM;
-      }
-      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(reinterpret_cast<uint8_t*>(cs_.t) + off, tb, kb, (int)c, 0, 64,
-                                                   st_));
-      KC_TRY(cold_.add_run(kb.Current(), c, st_));
-    }
-    KC_TRY(cs_.clear(st_));
+    KC_TRY(sp_.flush(cs_, hot_hard_, st_));
     cs_.count = 0;
-    ++sp_flushes_;
     return 0;
   }
 
@@ -1781,41 +1702,37 @@ class ShardT final : public ShardBase {
   // scans) against the cold tier; those found lose.  *changed: some did.
   int spill_check(uint64_t n, unsigned tiles, unsigned rgrid, bool* changed) {
     *changed = false;
-    KC_HIP_TRY(hipMemcpyAsync(h_spctr_ + 2, &d_ctr_->level_new, 8, hipMemcpyDeviceToHost, st_));
+    KC_HIP_TRY(hipMemcpyAsync(sp_.h_spctr + 2, &d_ctr_->level_new, 8, hipMemcpyDeviceToHost, st_));
     KC_HIP_TRY(hipStreamSynchronize(st_));
-    const uint64_t m = h_spctr_[2];
+    const uint64_t m = sp_.h_spctr[2];
     cs_.count += m;                   // the hot slots this level filled
-    sp_queries_ += m;
+    sp_.queries += m;
     if (cand_) sp_ratio_ = std::min(1.0, (double)m / (double)cand_);
     if (cs_.count > hot_hard_) {
       set_error("kc_shard: one level put %llu fingerprints into a hot seen-set of %llu slots; raise seen_hbm_bytes",
                 (unsigned long long)m, (unsigned long long)cs_.nslots);
       return -ENOMEM;
     }
-    if (m == 0 || cold_.empty()) return 0;
-    uint64_t* qk = reinterpret_cast<uint64_t*>(sp_arena_);
-    uint64_t* qk2 = qk + q_max_;
-    uint64_t* ql = qk2 + q_max_;
-    uint64_t* ql2 = ql + q_max_;
-    uint8_t* found = reinterpret_cast<uint8_t*>(ql2 + q_max_);
-    uint8_t* tmp = found + (q_max_ + 255) / 256 * 256;
+    if (m == 0 || sp_.cold.empty()) return 0;
+    const auto q = sp_.carve();
+    const uint64_t q_max = sp_.q_max;
     const unsigned lb = n_ ? tiles : 0u;
     // windows from the last to the first: a winner that loses clears its
     // bit, which would shift the positions of its parent's later winners,
     // so every window is taken before any lower one changes
-    const uint64_t nwin = (m + q_max_ - 1) / q_max_;
+    const uint64_t nwin = (m + q_max - 1) / q_max;
     for (uint64_t wi = nwin; wi-- > 0;) {
-      const uint64_t w0 = wi * q_max_, w1 = std::min(m, w0 + q_max_), c = w1 - w0;
-      hipLaunchKernelGGL(k_shard_spill_queries<M>, dim3(std::max(lb + rgrid, 1u)), dim3(256), 0, st_, cur_, n_, lb,
-                         flags_, newmask_, offsets_, n, rfp_, isnew_, ioff_, d_ctr_, w0, w1, qk, ql);
-      hipcub::DoubleBuffer<uint64_t> kb(qk, qk2);
-      hipcub::DoubleBuffer<uint64_t> vb(ql, ql2);
-      size_t tb = sp_qtmp_bytes_;
-      KC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kb, vb, (int)c, 0, 64, st_));
-      KC_HIP_TRY(hipMemsetAsync(found, 0, c, st_));
-      KC_TRY(cold_.probe(kb.Current(), c, found, d_spctr_, st_));
+      const uint64_t w0 = wi * q_max, w1 = std::min(m, w0 + q_max), c = w1 - w0;
+      hipLaunchKernelGGL(k_shard_spill_queries<M>, dim3(std::max(lb + rgrid, 1u)), dim3(256), 0, st_, cur_.p, n_, lb,
+                         flags_, newmask_.p, offsets_.p, n, rfp_.p, isnew_.p, ioff_.p, d_ctr_.p, w0, w1, q.qk, q.ql);
+      hipcub::DoubleBuffer<uint64_t> kb(q.qk, q.qk2);
+      hipcub::DoubleBuffer<uint64_t> vb(q.ql, q.ql2);
+      size_t tb = sp_.sp_qtmp_bytes;
+      KC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(q.tmp, tb, kb, vb, (int)c, 0, 64, st_));
+      KC_HIP_TRY(hipMemsetAsync(q.found, 0, c, st_));
+      KC_TRY(sp_.cold.probe(kb.Current(), c, q.found, sp_.d_spctr, st_));
       hipLaunchKernelGGL(k_shard_spill_apply, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, st_, kb.Current(),
-                         vb.Current(), found, c, newmask_, isnew_, cs_.t, cs_.nslots, d_ctr_);
+                         vb.Current(), q.found, c, newmask_.p, isnew_.p, cs_.t, cs_.nslots, d_ctr_.p);
       KC_HIP_TRY(hipGetLastError());
     }
     *changed = true;
@@ -1826,11 +1743,11 @@ class ShardT final : public ShardBase {
   int sn_setup(uint32_t cap) override {
     KC_HIP_TRY(hipSetDevice(cfg_.device));
     sn_cap_ = std::max<uint32_t>(1, std::min<uint32_t>(cap, SN_SLOT_MAX));
-    KC_HIP_TRY(hipMalloc(&d_snc_, sizeof(SNCtl)));
-    KC_HIP_TRY(hipHostMalloc(&h_snc_, sizeof(SNCtl)));
-    KC_HIP_TRY(hipMalloc(&d_sns_, sizeof(SNScratch)));
-    KC_HIP_TRY(hipMalloc(&sn_send_, (uint64_t)world_ * sn_slot_bytes()));
-    KC_HIP_TRY(hipMalloc(&sn_recv_, (uint64_t)world_ * sn_slot_bytes()));
+    KC_TRY(d_snc_.alloc(1));
+    KC_TRY(h_snc_.alloc(1));
+    KC_TRY(d_sns_.alloc(1));
+    KC_TRY(sn_send_.alloc((uint64_t)world_ * sn_slot_bytes() / 8));
+    KC_TRY(sn_recv_.alloc((uint64_t)world_ * sn_slot_bytes() / 8));
     KC_HIP_TRY(hipMemset(d_snc_, 0, sizeof(SNCtl)));
     KC_HIP_TRY(hipMemset(sn_send_, 0, (uint64_t)world_ * sn_slot_bytes()));
     KC_HIP_TRY(hipMemset(sn_recv_, 0, (uint64_t)world_ * sn_slot_bytes()));
@@ -1855,9 +1772,9 @@ class ShardT final : public ShardBase {
     const uint64_t per = SN_CAND_MAX + in + 1;           // new states one level may add, at most
     const uint64_t bufs = std::max<uint64_t>(SN_MAX, per);
     const uint64_t base = level_base_.back();
-    if (!rc) rc = grow_buffer(cur_, cur_cap_, bufs, true, st_);
-    if (!rc) rc = grow_buffer(next_, next_cap_, bufs, false, st_);
-    if (!rc) rc = grow_buffer(pkeys_, pk_cap_, base + n_ + (uint64_t)batch * per + 1, true, st_);
+    if (!rc) rc = cur_.grow(bufs, st_, true);
+    if (!rc) rc = next_.grow(bufs, st_);
+    if (!rc) rc = pkeys_.grow(base + n_ + (uint64_t)batch * per + 1, st_, true);
     // ClaimSet room for the batch: a few times the first level's bound, not
     // the batch's worst case (that forced ~2M entries on every model; ADVICE
     // r4).  The device stops a level whose claims might not fit (room below,
@@ -1882,8 +1799,8 @@ class ShardT final : public ShardBase {
       h.fail = 1;           // (buf_cap = room = par_cap = 0: nothing runs)
     } else {
       h.room = cs_.capacity() / 2 > cs_.count ? cs_.capacity() / 2 - cs_.count : 0;
-      h.buf_cap = std::min(cur_cap_, next_cap_);
-      h.par_cap = pk_cap_;
+      h.buf_cap = std::min(cur_.cap, next_.cap);
+      h.par_cap = pkeys_.cap;
     }
     sn_n0_ = n_;
     KC_HIP_TRY(hipMemcpyAsync(d_snc_, h_snc_, offsetof(SNCtl, lwidths), hipMemcpyHostToDevice, st_));
@@ -1936,8 +1853,7 @@ class ShardT final : public ShardBase {
     n_ = h.n;
     cand_ = h.cand;
     if (h.levels & 1) {
-      std::swap(cur_, next_);
-      std::swap(cur_cap_, next_cap_);
+      cur_.swap(next_);
     }
     out->status_new = n_;
     out->status_err = h.err[(h.level - 1) & 1];
@@ -1951,24 +1867,19 @@ class ShardT final : public ShardBase {
 
   int advance() override {
     level_base_.push_back(level_base_.back() + n_);
-    std::swap(cur_, next_);
-    std::swap(cur_cap_, next_cap_);
+    cur_.swap(next_);
     if (emitted_links_) {
       // the new frontier is links into the old one (now next_) and into the
       // receive buffer; this level's plans become the previous level's
-      std::swap(link_cur_, link_next_);
-      std::swap(link_cur_cap_, link_next_cap_);
-      std::swap(pc_cur_, pc_prev_);
-      std::swap(pc_cur_cap_, pc_prev_cap_);
+      link_cur_.swap(link_next_);
+      pc_cur_.swap(pc_prev_);
       prev_rec_ = last_in_;
       cur_deferred_ = next_n_ > 0;
       emitted_links_ = false;
     }
     if (tlc_) {
-      std::swap(gbits_cur_, gbits_next_);
-      std::swap(gbits_cur_cap_, gbits_next_cap_);
-      std::swap(grank_cur_, grank_next_);
-      std::swap(grank_cur_cap_, grank_next_cap_);
+      gbits_cur_.swap(gbits_next_);
+      grank_cur_.swap(grank_next_);
     }
     n_ = next_n_;
     cand_ = next_cand_;
@@ -2002,7 +1913,7 @@ class ShardT final : public ShardBase {
       cur_deferred_ = false;
       return 0;
     }
-    KC_TRY(grow_buffer(cur_, cur_cap_, n_, false, st_));
+    KC_TRY(cur_.grow(n_, st_));
     DeferArgs df;
     df.prev = next_;
     df.link = link_cur_;
@@ -2043,7 +1954,7 @@ class ShardT final : public ShardBase {
       set_error("kc_shard tlc_masks: %s", tlc_ ? "a level of 2^31 states or more" : "not in TLC order");
       return -EINVAL;
     }
-    KC_TRY(grow_buffer(wmask_, wmask_cap_, W, false, st_));
+    KC_TRY(wmask_.grow(W, st_));
     KC_HIP_TRY(hipMemsetAsync(wmask_, 0, W * 4, st_));
     const uint64_t next_gidx = level_base_.back() + n_;
     if (next_n_)
@@ -2057,34 +1968,33 @@ class ShardT final : public ShardBase {
     KC_HIP_TRY(hipSetDevice(cfg_.device));
     // (the next level has at most 32 W states: W + 1 bitmap words)
     const uint64_t words = W + 1;
-    KC_TRY(grow_buffer(gbits_next_, gbits_next_cap_, words, false, st_));
-    KC_TRY(grow_buffer(grank_next_, grank_next_cap_, words, false, st_));
-    KC_TRY(grow_buffer(wbase_, wbase_cap_, W, false, st_));
+    KC_TRY(gbits_next_.grow(words, st_));
+    KC_TRY(grank_next_.grow(words, st_));
+    KC_TRY(wbase_.grow(W, st_));
     KC_HIP_TRY(hipMemsetAsync(gbits_next_, 0, words * 4, st_));
     size_t tmp_bytes = 0;
     const hipcub::TransformInputIterator<uint32_t, NewCount, const uint32_t*> wc(wmask_, NewCount());
-    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, wc, wbase_, (int)W, st_));
-    KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, wc, wbase_, (int)W, st_));
+    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, wc, wbase_.p, (int)W, st_));
+    KC_TRY(scan_tmp_.grow(tmp_bytes + 16, st_));
+    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_.p, tmp_bytes, wc, wbase_.p, (int)W, st_));
     const uint64_t nn = next_n_, next_gidx = level_base_.back() + n_;
     const unsigned g = (unsigned)((nn + 255) / 256);
     if (nn) {
-      KC_TRY(grow_buffer(gnew_, gnew_cap_, nn, false, st_));
+      KC_TRY(gnew_.grow(nn, st_));
       hipLaunchKernelGGL(k_tlc_pos, dim3(g), dim3(256), 0, st_, pkeys_ + next_gidx, nn, wmask_, wbase_, gnew_,
                          gbits_next_);
     }
     const hipcub::TransformInputIterator<uint32_t, NewCount, const uint32_t*> bc(gbits_next_, NewCount());
-    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, bc, grank_next_, (int)words, st_));
-    KC_TRY(grow_buffer(scan_tmp_, scan_cap_, tmp_bytes + 16, false, st_));
-    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_, tmp_bytes, bc, grank_next_, (int)words, st_));
+    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, bc, grank_next_.p, (int)words, st_));
+    KC_TRY(scan_tmp_.grow(tmp_bytes + 16, st_));
+    KC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp_.p, tmp_bytes, bc, grank_next_.p, (int)words, st_));
     if (nn) {
-      KC_TRY(grow_buffer(link_tmp_, link_tmp_cap_, std::max(nn, link_next_cap_), false, st_));
-      KC_TRY(grow_buffer(pk_tmp_, pk_tmp_cap_, nn, false, st_));
+      KC_TRY(link_tmp_.grow(std::max(nn, link_next_.cap), st_));
+      KC_TRY(pk_tmp_.grow(nn, st_));
       hipLaunchKernelGGL(k_tlc_perm, dim3(g), dim3(256), 0, st_, nn, gnew_, gbits_next_, grank_next_, link_next_,
                          pkeys_ + next_gidx, link_tmp_, pk_tmp_, gpos_all_ + next_gidx);
       KC_HIP_TRY(hipMemcpyAsync(pkeys_ + next_gidx, pk_tmp_, nn * 8, hipMemcpyDeviceToDevice, st_));
-      std::swap(link_next_, link_tmp_);
-      std::swap(link_next_cap_, link_tmp_cap_);
+      link_next_.swap(link_tmp_);
     }
     KC_HIP_TRY(hipGetLastError());
     KC_HIP_TRY(hipStreamSynchronize(st_));
@@ -2156,13 +2066,13 @@ class ShardT final : public ShardBase {
     r->fpset_slots = cs_.capacity();
     if (spill_) {
       ColdStats cst;
-      cold_.stats(&cst);
+      sp_.cold.stats(&cst);
       unsigned long long hits = 0;
-      KC_HIP_TRY(hipMemcpy(&hits, d_spctr_, 8, hipMemcpyDeviceToHost));
-      r->seen_flushes = sp_flushes_;
+      KC_HIP_TRY(hipMemcpy(&hits, sp_.d_spctr, 8, hipMemcpyDeviceToHost));
+      r->seen_flushes = sp_.flushes;
       r->seen_cold_fps = cst.keys;
       r->seen_cold_runs = cst.runs;
-      r->seen_cold_queries = sp_queries_;
+      r->seen_cold_queries = sp_.queries;
       r->seen_cold_hits = hits;
       r->seen_merges = cst.merges;
       r->seen_disk_bytes = cst.disk_written;
@@ -2176,94 +2086,61 @@ class ShardT final : public ShardBase {
   }
 
  private:
+  // What is not a buffer.  The buffers free themselves after this, with the
+  // device still current; the stream (st_, declared before them) goes last.
   void release() {
     (void)hipSetDevice(cfg_.device);
     cs_.release();
-    for (void* p : {(void*)cur_, (void*)next_, (void*)pkeys_, (void*)cnt_, (void*)off_,
-                    (void*)ovf_fp_, (void*)ovf_lk_, (void*)ovf_tile_, (void*)d_ovf_cnt_,
-                    (void*)repmask_, (void*)newmask_, (void*)offsets_, (void*)rcount_, (void*)rec_fp_,
-                    (void*)rec_lk_, (void*)rfp_, (void*)flag_, (void*)isnew_, (void*)ioff_,
-                    (void*)scan_tmp_, (void*)d_ctr_, (void*)d_owner_base_, (void*)stage_, (void*)d_stage_cur_,
-                    (void*)tcnt_, (void*)toff_, (void*)stoff_, (void*)ocsum_, (void*)wtot_, (void*)woff_, (void*)link_cur_,
-                    (void*)link_next_, (void*)pc_cur_, (void*)pc_prev_, (void*)d_dchk_, (void*)d_ctr_dbg_,
-                    (void*)pk_dbg_, (void*)gpos_all_, (void*)gbits_cur_, (void*)grank_cur_, (void*)gbits_next_,
-                    (void*)grank_next_, (void*)wmask_, (void*)wbase_, (void*)gnew_, (void*)link_tmp_,
-                    (void*)pk_tmp_})
-      if (p) (void)hipFree(p);
-    if (h_ctr_) (void)hipHostFree(h_ctr_);
-    if (h_exp_) (void)hipHostFree(h_exp_);
-    if (h_owner_base_) (void)hipHostFree(h_owner_base_);
-    for (void* p : {(void*)d_snc_, (void*)d_sns_, (void*)sn_send_, (void*)sn_recv_})
-      if (p) (void)hipFree(p);
-    if (h_snc_) (void)hipHostFree(h_snc_);
-    if (sp_arena_) (void)hipFree(sp_arena_);
-    if (d_spctr_) (void)hipFree(d_spctr_);
-    if (h_spctr_) (void)hipHostFree(h_spctr_);
     for (auto& e : ev_)
       if (e) (void)hipEventDestroy(e);
-    if (st_ && own_st_) (void)hipStreamDestroy(st_);
   }
 
   kc_model_config cfg_;
   int rank_, world_;
   Flags flags_{};
-  hipStream_t st_ = nullptr;
-  bool own_st_ = true;
+  OwnedStream st_;   // (before every buffer: destroyed after them; set_stream: the caller's, not ours)
   DevClaimSet cs_;
-  State *cur_ = nullptr, *next_ = nullptr;
-  uint64_t cur_cap_ = 0, next_cap_ = 0;
-  unsigned long long* pkeys_ = nullptr;
-  uint64_t pk_cap_ = 0;
+  DeviceArray<State> cur_, next_;
+  DeviceArray<unsigned long long> pkeys_;
   // expand: owner counts / scan, remote representatives, local claim tiles
-  uint8_t* cnt_ = nullptr;
-  uint32_t *off_ = nullptr, *repmask_ = nullptr, *newmask_ = nullptr, *offsets_ = nullptr;
-  uint64_t cnt_cap_ = 0, off_cap_ = 0, rm_cap_ = 0, mask_cap_ = 0, offsets_cap_ = 0;
-  unsigned int *rcount_ = nullptr, *rec_lk_ = nullptr;
-  unsigned long long* rec_fp_ = nullptr;
-  uint64_t rcount_cap_ = 0, rec_fp_cap_ = 0, rec_lk_cap_ = 0;
+  DeviceArray<uint8_t> cnt_;
+  DeviceArray<uint32_t> off_, repmask_, newmask_, offsets_;
+  DeviceArray<unsigned int> rcount_, rec_lk_;
+  DeviceArray<unsigned long long> rec_fp_;
   CandOvf ovf_{};
-  unsigned long long* ovf_fp_ = nullptr;
-  unsigned int *ovf_lk_ = nullptr, *ovf_tile_ = nullptr;
-  uint64_t ovf_fp_cap_ = 0, ovf_lk_cap_ = 0, ovf_tile_cap_ = 0;
-  unsigned long long* d_ovf_cnt_ = nullptr;
+  DeviceArray<unsigned long long> ovf_fp_;
+  DeviceArray<unsigned int> ovf_lk_, ovf_tile_;
+  DeviceArray<unsigned long long> d_ovf_cnt_;
   // insert: per received record
-  unsigned long long* rfp_ = nullptr;
-  unsigned int* flag_ = nullptr;
-  uint32_t *isnew_ = nullptr, *ioff_ = nullptr;
-  uint64_t rfp_cap_ = 0, flag_cap_ = 0, isnew_cap_ = 0, ioff_cap_ = 0;
-  uint8_t* scan_tmp_ = nullptr;
-  uint64_t scan_cap_ = 0;
+  DeviceArray<unsigned long long> rfp_;
+  DeviceArray<unsigned int> flag_;
+  DeviceArray<uint32_t> isnew_, ioff_;
+  DeviceArray<uint8_t> scan_tmp_;
   // record staging (ShardArgs::stage; world > 1)
-  Rec* stage_ = nullptr;
-  uint64_t stage_cap_ = 0;
-  unsigned long long* d_stage_cur_ = nullptr;
-  uint32_t *tcnt_ = nullptr, *toff_ = nullptr;
-  uint64_t tcnt_cap_ = 0, toff_cap_ = 0;
+  DeviceArray<Rec> stage_;
+  DeviceArray<unsigned long long> d_stage_cur_;
+  DeviceArray<uint32_t> tcnt_, toff_;
   // owner x chunk sums of the staged record counts (k_owner_cscan; zeroed at
-  // allocation and by each scan); KC_CHUNK_SCAN=0: k_owner_tscan per tile
+  // allocation, at every run's start and by each scan); KC_CHUNK_SCAN=0:
+  // k_owner_tscan per tile
   bool ocscan_ = true, ocscan_level_ = false;
-  uint32_t* ocsum_ = nullptr;
-  uint64_t ocsum_cap_ = 0;
-  unsigned long long* stoff_ = nullptr;
-  uint64_t stoff_cap_ = 0;
+  DeviceArray<uint32_t> ocsum_;
+  DeviceArray<unsigned long long> stoff_;
   bool stage_on_ = true, stage_level_ = false, staged_ = false;
   bool first_ = false;    // first-claim mode (cfg.first_claim)
   uint64_t stage_fallbacks_ = 0;       // levels packed the old way (staging estimate exceeded)
   double rec_ratio_ = 1.0;             // records sent per parent, last level (the staging estimate)
   // the tile-count insert path: own tiles' and record blocks' new-state counts, their scan
   bool tcount_ = true;
-  uint32_t *wtot_ = nullptr, *woff_ = nullptr;
-  uint64_t wtot_cap_ = 0, woff_cap_ = 0;
+  DeviceArray<uint32_t> wtot_, woff_;
   // the deferred frontier (set_deferred; the native loop's counted levels)
   bool defer_on_ = false;
   bool cur_deferred_ = false;        // cur_ not built: link_cur_ into next_ (the previous frontier) / prev_rec_
   bool emitted_links_ = false;       // the last insert emitted links (advance swaps them in)
   bool rebuilt_ = false;             // this level's k_claim rebuilt its parents
   bool cand_est_ = false, next_cand_est_ = false;   // cand_ / next_cand_ estimated, not counted
-  unsigned long long *link_cur_ = nullptr, *link_next_ = nullptr;
-  uint64_t link_cur_cap_ = 0, link_next_cap_ = 0;
-  unsigned long long *pc_cur_ = nullptr, *pc_prev_ = nullptr;   // plans of this / the previous level's parents
-  uint64_t pc_cur_cap_ = 0, pc_prev_cap_ = 0;
+  DeviceArray<unsigned long long> link_cur_, link_next_;
+  DeviceArray<unsigned long long> pc_cur_, pc_prev_;   // plans of this / the previous level's parents
   const Rec* prev_rec_ = nullptr;    // the receive buffer the links point into
   const Rec* last_in_ = nullptr;     // the last insert's receive buffer
   uint64_t defer_err_ = ~0ull;       // expand_done: the rebuild's invariant key
@@ -2276,22 +2153,18 @@ class ShardT final : public ShardBase {
   // TLC order (tlc_*): G of every state (parallel to pkeys_), the current /
   // next level's G -> local index map, the per-parent masks and scratch
   bool tlc_ = false;
-  uint32_t* gpos_all_ = nullptr;
-  uint64_t gp_cap_ = 0;
-  uint32_t *gbits_cur_ = nullptr, *grank_cur_ = nullptr, *gbits_next_ = nullptr, *grank_next_ = nullptr;
-  uint64_t gbits_cur_cap_ = 0, grank_cur_cap_ = 0, gbits_next_cap_ = 0, grank_next_cap_ = 0;
-  uint32_t *wmask_ = nullptr, *wbase_ = nullptr, *gnew_ = nullptr;
-  uint64_t wmask_cap_ = 0, wbase_cap_ = 0, gnew_cap_ = 0;
-  unsigned long long *link_tmp_ = nullptr, *pk_tmp_ = nullptr;
-  uint64_t link_tmp_cap_ = 0, pk_tmp_cap_ = 0;
-  unsigned long long* d_dchk_ = nullptr;
-  Counters* d_ctr_dbg_ = nullptr;
-  unsigned long long* pk_dbg_ = nullptr;
-  uint64_t pk_dbg_cap_ = 0;
-  uint64_t* d_owner_base_ = nullptr;   // per-owner record totals (device / pinned host)
-  uint64_t* h_owner_base_ = nullptr;
-  Counters *d_ctr_ = nullptr, *h_ctr_ = nullptr;
-  Counters* h_exp_ = nullptr;          // pinned: expand's level head (kCtrHead bytes)
+  DeviceArray<uint32_t> gpos_all_;
+  DeviceArray<uint32_t> gbits_cur_, grank_cur_, gbits_next_, grank_next_;
+  DeviceArray<uint32_t> wmask_, wbase_, gnew_;
+  DeviceArray<unsigned long long> link_tmp_, pk_tmp_;
+  DeviceArray<unsigned long long> d_dchk_;
+  DeviceArray<Counters> d_ctr_dbg_;
+  DeviceArray<unsigned long long> pk_dbg_;
+  DeviceArray<uint64_t> d_owner_base_;   // per-owner record totals (device / pinned host)
+  PinnedArray<uint64_t> h_owner_base_;
+  DeviceArray<Counters> d_ctr_;
+  PinnedArray<Counters> h_ctr_;
+  PinnedArray<Counters> h_exp_;        // expand's level head (kCtrHead bytes)
   uint64_t n_ = 0, next_n_ = 0, send_total_ = 0, gen_init_ = 0;
   uint64_t cand_ = 0, next_cand_ = 0, cand_total_ = 0;   // successors of the frontier
   uint64_t init_err_ = ~0ull;
@@ -2305,9 +2178,10 @@ class ShardT final : public ShardBase {
   hipEvent_t ev_[2] = {nullptr, nullptr};
   bool async_pack_ = false;
   // device-driven narrow levels
-  SNCtl *d_snc_ = nullptr, *h_snc_ = nullptr;
-  SNScratch* d_sns_ = nullptr;
-  uint64_t *sn_send_ = nullptr, *sn_recv_ = nullptr;
+  DeviceArray<SNCtl> d_snc_;
+  PinnedArray<SNCtl> h_snc_;
+  DeviceArray<SNScratch> d_sns_;
+  DeviceArray<uint64_t> sn_send_, sn_recv_;
   uint32_t sn_cap_ = SN_SLOT_DEFAULT;
   uint64_t sn_n0_ = 0;
   double claim_ms_ = 0;
@@ -2316,13 +2190,8 @@ class ShardT final : public ShardBase {
   // seen-set spill
   bool spill_ = false;
   std::string spill_dir_;
-  ColdSet cold_;
-  uint64_t hot_limit_ = 0, hot_hard_ = 0, q_max_ = 0;
-  uint8_t* sp_arena_ = nullptr;
-  uint64_t sp_arena_bytes_ = 0;
-  size_t sp_qtmp_bytes_ = 0;
-  unsigned long long *d_spctr_ = nullptr, *h_spctr_ = nullptr;   // [0] cold hits, [1] flush count, [2] m
-  uint64_t sp_flushes_ = 0, sp_queries_ = 0;
+  SeenSpill<uint64_t> sp_;
+  uint64_t hot_hard_ = 0;           // most hot entries a level may leave (7/8 of the slots)
   double sp_ratio_ = 1.0;           // hot slots filled per successor, last level
 };
 

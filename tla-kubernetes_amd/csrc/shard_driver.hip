@@ -57,9 +57,8 @@ constexpr uint64_t PIECE_BYTES = 64ull << 20;
 // KC_PIECE_BYTES from the environment (tests shrink it so a small model runs
 // the multi-piece path).
 uint64_t piece_bytes() {
-  const char* e = getenv("KC_PIECE_BYTES");
-  const long long v = e ? atoll(e) : 0;
-  return v > 0 ? (uint64_t)v : PIECE_BYTES;
+  const uint64_t v = env_u64("KC_PIECE_BYTES");
+  return v ? v : PIECE_BYTES;
 }
 
 // ---------------------------------------------------------------- RCCL
@@ -248,12 +247,6 @@ __global__ void __launch_bounds__(256) k_sum_u32(SumBufs b, uint64_t n) {
 class LocalComm final : public Comm {
  public:
   explicit LocalComm(std::vector<ShardBase*> shards) : s_(std::move(shards)) {}
-  ~LocalComm() override {
-    if (rows_) (void)hipFree(rows_);
-    if (hrows_) (void)hipHostFree(hrows_);
-    if (xd_) (void)hipFree(xd_);
-    if (xh_) (void)hipHostFree(xh_);
-  }
   int all_gather(const std::vector<std::vector<uint64_t>>& rows, std::vector<uint64_t>& out) override {
     out.clear();
     for (const auto& r : rows) out.insert(out.end(), r.begin(), r.end());
@@ -263,14 +256,12 @@ class LocalComm final : public Comm {
   // kernels write in the RCCL path, k_owner_totals, are exercised here)
   uint64_t* row_buffer(size_t i, size_t L) override {
     const size_t need = s_.size() * L;
-    if (need > rows_cap_) {
-      if (rows_) (void)hipFree(rows_);
-      if (hrows_) (void)hipHostFree(hrows_);
-      rows_ = nullptr;
-      hrows_ = nullptr;
-      rows_cap_ = 0;
-      if (hipMalloc(&rows_, need * 8) != hipSuccess || hipHostMalloc(&hrows_, need * 8) != hipSuccess) return nullptr;
-      rows_cap_ = need;
+    if (need > std::min(rows_.cap, hrows_.cap)) {
+      if (rows_.renew(need) < 0 || hrows_.renew(need) < 0) {
+        rows_.reset();
+        hrows_.reset();
+        return nullptr;
+      }
     }
     return rows_ + i * L;
   }
@@ -278,7 +269,7 @@ class LocalComm final : public Comm {
     for (size_t i = 0; i < s_.size(); ++i)
       KC_HIP_TRY(hipMemcpyAsync(hrows_ + i * L, rows_ + i * L, L * 8, hipMemcpyDeviceToHost, s_[i]->stream()));
     for (auto* s : s_) KC_HIP_TRY(hipStreamSynchronize(s->stream()));
-    out.assign(hrows_, hrows_ + s_.size() * L);
+    out.assign(hrows_.p, hrows_.p + s_.size() * L);
     return 0;
   }
   // every rank's exchange plan, its pieces paired as RCCL pairs them: the
@@ -368,31 +359,25 @@ class LocalComm final : public Comm {
       set_error("emulated exchange: %llu chunks in one launch", (unsigned long long)chunks);
       return -EIO;
     }
-    if (xfers_.size() > xcap_) {
-      if (xd_) KC_HIP_TRY(hipFree(xd_));
-      if (xh_) KC_HIP_TRY(hipHostFree(xh_));
-      xd_ = nullptr;
-      xh_ = nullptr;
-      xcap_ = std::max<size_t>(2 * xfers_.size(), 256);
-      KC_HIP_TRY(hipMalloc(&xd_, xcap_ * sizeof(CopyXfer)));
-      KC_HIP_TRY(hipHostMalloc(&xh_, xcap_ * sizeof(CopyXfer)));
+    if (xfers_.size() > std::min(xd_.cap, xh_.cap)) {
+      const size_t xcap = std::max<size_t>(2 * xfers_.size(), 256);
+      KC_TRY(xd_.renew(xcap));
+      KC_TRY(xh_.renew(xcap));
     }
     memcpy(xh_, xfers_.data(), xfers_.size() * sizeof(CopyXfer));
     hipStream_t st = s_[0]->stream();
     KC_HIP_TRY(hipMemcpyAsync(xd_, xh_, xfers_.size() * sizeof(CopyXfer), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_multi_copy, dim3((unsigned)chunks), dim3(256), 0, st, xd_, (int)xfers_.size());
+    hipLaunchKernelGGL(k_multi_copy, dim3((unsigned)chunks), dim3(256), 0, st, xd_.p, (int)xfers_.size());
     KC_HIP_TRY(hipGetLastError());
     KC_HIP_TRY(hipStreamSynchronize(st));
     return 0;
   }
   std::vector<ShardBase*> s_;
-  uint64_t* rows_ = nullptr;
-  uint64_t* hrows_ = nullptr;
-  size_t rows_cap_ = 0;
+  DeviceArray<uint64_t> rows_;
+  PinnedArray<uint64_t> hrows_;
   std::vector<CopyXfer> xfers_;
-  CopyXfer* xd_ = nullptr;
-  CopyXfer* xh_ = nullptr;
-  size_t xcap_ = 0;
+  DeviceArray<CopyXfer> xd_;
+  PinnedArray<CopyXfer> xh_;
 };
 
 class RcclComm final : public Comm {
@@ -400,13 +385,9 @@ class RcclComm final : public Comm {
   // At world 1 every collective is the identity, done on the host; with
   // KC_RCCL_FORCE=1 they still go through RCCL (tests of the RCCL path).
   RcclComm(ShardBase* s, ncclComm_t c) : s_(s), comm_(c) {
-    const char* f = getenv("KC_RCCL_FORCE");
-    trivial_ = s->world() == 1 && !(f && f[0] == '1');
+    trivial_ = s->world() == 1 && !env_flag("KC_RCCL_FORCE", false);
   }
   ~RcclComm() override {
-    if (sink_) (void)hipFree(sink_);
-    if (buf_) (void)hipFree(buf_);
-    if (hbuf_) (void)hipHostFree(hbuf_);
     if (comm_ && rccl()) (void)rccl()->comm_destroy(comm_);
   }
   int all_gather(const std::vector<std::vector<uint64_t>>& rows, std::vector<uint64_t>& out) override {
@@ -442,7 +423,7 @@ class RcclComm final : public Comm {
   // for want of memory could not allocate it then), two halves of one piece.
   int make_sink() {
     if (trivial_ || sink_) return 0;
-    KC_HIP_TRY(hipMalloc(&sink_, 2 * piece_bytes()));
+    KC_TRY(sink_.alloc(2 * piece_bytes()));
     return 0;
   }
   int all_to_all(const std::vector<void*>& send, const std::vector<std::vector<uint64_t>>& Mx, uint64_t rb,
@@ -460,10 +441,10 @@ class RcclComm final : public Comm {
     KC_NCCL_TRY(rccl()->group_start());
     for (const auto& x : plan) {
       if (x.send)
-        KC_NCCL_TRY(rccl()->send(sk ? (const uint64_t*)sink_ : (const uint64_t*)send[0] + x.off * rw, x.n * rw,
+        KC_NCCL_TRY(rccl()->send(sk ? (const uint64_t*)sink_.p : (const uint64_t*)send[0] + x.off * rw, x.n * rw,
                                  ncclUint64, x.peer, comm_, st));
       else
-        KC_NCCL_TRY(rccl()->recv(sk ? (uint64_t*)sink_ + piece * rw : (uint64_t*)recv[0] + x.off * rw, x.n * rw,
+        KC_NCCL_TRY(rccl()->recv(sk ? (uint64_t*)sink_.p + piece * rw : (uint64_t*)recv[0] + x.off * rw, x.n * rw,
                                  ncclUint64, x.peer, comm_, st));
     }
     KC_NCCL_TRY(rccl()->group_end());
@@ -492,7 +473,7 @@ class RcclComm final : public Comm {
     uint32_t* p = buf[0];
     if (!p) {                      // a failed rank: zeroes, through the scratch
       KC_TRY(scratch((n + 1) / 2));
-      p = reinterpret_cast<uint32_t*>(buf_);
+      p = reinterpret_cast<uint32_t*>(buf_.p);
       KC_HIP_TRY(hipMemsetAsync(p, 0, n * 4, st));
     }
     KC_NCCL_TRY(rccl()->all_reduce(p, p, n, ncclUint32, ncclSum, comm_, st));
@@ -523,7 +504,7 @@ class RcclComm final : public Comm {
     KC_NCCL_TRY(rccl()->all_reduce(buf_, buf_, L, ncclUint64, ncclSum, comm_, st));
     KC_HIP_TRY(hipMemcpyAsync(hbuf_, buf_, L * 8, hipMemcpyDeviceToHost, st));
     KC_HIP_TRY(hipStreamSynchronize(st));
-    out.assign(hbuf_, hbuf_ + L);
+    out.assign(hbuf_.p, hbuf_.p + L);
     return 0;
   }
 
@@ -531,23 +512,17 @@ class RcclComm final : public Comm {
   // device scratch for the small collectives and a pinned host mirror, so
   // their host <-> device copies are asynchronous DMA (no pageable staging)
   int scratch(size_t words) {
-    if (words <= cap_) return 0;
-    if (buf_) KC_HIP_TRY(hipFree(buf_));
-    if (hbuf_) KC_HIP_TRY(hipHostFree(hbuf_));
-    buf_ = nullptr;
-    hbuf_ = nullptr;
-    cap_ = std::max<size_t>(words, 256);
-    KC_HIP_TRY(hipMalloc(&buf_, cap_ * 8));
-    KC_HIP_TRY(hipHostMalloc(&hbuf_, cap_ * 8));
-    return 0;
+    if (words <= std::min(buf_.cap, hbuf_.cap)) return 0;
+    const size_t cap = std::max<size_t>(words, 256);
+    KC_TRY(buf_.renew(cap));
+    return hbuf_.renew(cap);
   }
   ShardBase* s_;
   bool trivial_ = false;
   ncclComm_t comm_ = nullptr;
-  uint64_t* sink_ = nullptr;
-  uint64_t* buf_ = nullptr;
-  uint64_t* hbuf_ = nullptr;
-  size_t cap_ = 0;
+  DeviceArray<uint8_t> sink_;
+  DeviceArray<uint64_t> buf_;
+  PinnedArray<uint64_t> hbuf_;
 };
 
 // One shard per process; the collectives are the caller's (kc_host_comm:
@@ -560,12 +535,6 @@ class RcclComm final : public Comm {
 class HostComm final : public Comm {
  public:
   HostComm(ShardBase* s, const kc_host_comm& ops) : s_(s), ops_(ops) {}
-  ~HostComm() override {
-    if (drow_) (void)hipFree(drow_);
-    if (hrow_) (void)hipHostFree(hrow_);
-    if (hsend_) (void)hipHostFree(hsend_);
-    if (hrecv_) (void)hipHostFree(hrecv_);
-  }
   int all_gather(const std::vector<std::vector<uint64_t>>& rows, std::vector<uint64_t>& out) override {
     const size_t L = rows[0].size();
     out.assign(L * (size_t)s_->world(), 0);
@@ -573,14 +542,12 @@ class HostComm final : public Comm {
   }
   uint64_t* row_buffer(size_t i, size_t L) override {
     if (i != 0) return nullptr;
-    if (L > row_cap_) {
-      if (drow_) (void)hipFree(drow_);
-      if (hrow_) (void)hipHostFree(hrow_);
-      drow_ = nullptr;
-      hrow_ = nullptr;
-      row_cap_ = 0;
-      if (hipMalloc(&drow_, L * 8) != hipSuccess || hipHostMalloc(&hrow_, L * 8) != hipSuccess) return nullptr;
-      row_cap_ = L;
+    if (L > std::min(drow_.cap, hrow_.cap)) {
+      if (drow_.renew(L) < 0 || hrow_.renew(L) < 0) {
+        drow_.reset();
+        hrow_.reset();
+        return nullptr;
+      }
     }
     return drow_;
   }
@@ -599,8 +566,8 @@ class HostComm final : public Comm {
       ns += Mx[me][p];
       nr += Mx[p][me];
     }
-    KC_TRY(pinned(hsend_, hsend_cap_, ns * rb));
-    KC_TRY(pinned(hrecv_, hrecv_cap_, nr * rb));
+    KC_TRY(pinned(hsend_, ns * rb));
+    KC_TRY(pinned(hrecv_, nr * rb));
     hipStream_t st = s_->stream();
     if (ns) KC_HIP_TRY(hipMemcpyAsync(hsend_, send[0], ns * rb, hipMemcpyDeviceToHost, st));
     KC_HIP_TRY(hipStreamSynchronize(st));            // every record packed and staged
@@ -612,7 +579,7 @@ class HostComm final : public Comm {
       xf[4 * k + 2] = plan[k].off * rb;
       xf[4 * k + 3] = plan[k].n * rb;
     }
-    KC_TRY(call(ops_.exchange(ops_.ctx, xf.data(), (int)plan.size(), hsend_, hrecv_), "exchange"));
+    KC_TRY(call(ops_.exchange(ops_.ctx, xf.data(), (int)plan.size(), hsend_.p, hrecv_.p), "exchange"));
     if (nr) KC_HIP_TRY(hipMemcpyAsync(recv[0], hrecv_, nr * rb, hipMemcpyHostToDevice, st));
     return 0;                                        // stream-ordered before insert
   }
@@ -620,8 +587,8 @@ class HostComm final : public Comm {
   int sn_exchange(const std::vector<void*>& send, const std::vector<void*>& recv, uint64_t slot) override {
     const int R = s_->world(), me = s_->rank();
     if (R == 1) return 0;
-    KC_TRY(pinned(hsend_, hsend_cap_, R * slot));
-    KC_TRY(pinned(hrecv_, hrecv_cap_, R * slot));
+    KC_TRY(pinned(hsend_, R * slot));
+    KC_TRY(pinned(hrecv_, R * slot));
     hipStream_t st = s_->stream();
     KC_HIP_TRY(hipMemcpyAsync(hsend_, send[0], R * slot, hipMemcpyDeviceToHost, st));
     KC_HIP_TRY(hipStreamSynchronize(st));
@@ -635,7 +602,7 @@ class HostComm final : public Comm {
         xf.push_back(slot);
       }
     }
-    KC_TRY(call(ops_.exchange(ops_.ctx, xf.data(), (int)(xf.size() / 4), hsend_, hrecv_), "exchange"));
+    KC_TRY(call(ops_.exchange(ops_.ctx, xf.data(), (int)(xf.size() / 4), hsend_.p, hrecv_.p), "exchange"));
     KC_HIP_TRY(hipMemcpyAsync(recv[0], hrecv_, R * slot, hipMemcpyHostToDevice, st));
     return 0;
   }
@@ -690,23 +657,16 @@ class HostComm final : public Comm {
   }
   // pinned staging, grown (the previous contents are not kept); the stream
   // is idle here: every use follows a synchronisation of it
-  int pinned(uint8_t*& p, uint64_t& cap, uint64_t bytes) {
-    if (bytes <= cap) return 0;
+  int pinned(PinnedArray<uint8_t>& a, uint64_t bytes) {
+    if (bytes <= a.cap) return 0;
     KC_HIP_TRY(hipStreamSynchronize(s_->stream()));
-    if (p) KC_HIP_TRY(hipHostFree(p));
-    p = nullptr;
-    cap = std::max<uint64_t>(bytes, 2 * cap);
-    KC_HIP_TRY(hipHostMalloc(&p, cap));
-    return 0;
+    return a.renew(std::max<uint64_t>(bytes, 2 * a.cap));
   }
   ShardBase* s_;
   kc_host_comm ops_;
-  uint64_t* drow_ = nullptr;
-  uint64_t* hrow_ = nullptr;
-  size_t row_cap_ = 0;
-  uint8_t* hsend_ = nullptr;
-  uint8_t* hrecv_ = nullptr;
-  uint64_t hsend_cap_ = 0, hrecv_cap_ = 0;
+  DeviceArray<uint64_t> drow_;
+  PinnedArray<uint64_t> hrow_;
+  PinnedArray<uint8_t> hsend_, hrecv_;
 };
 
 }  // namespace
@@ -716,8 +676,7 @@ class Group {
  public:
   Group(std::vector<ShardBase*> local, std::unique_ptr<Comm> comm, const kc_model_config& cfg)
       : local_(std::move(local)), comm_(std::move(comm)), cfg_(cfg) {
-    const char* dr = getenv("KC_DEVROW");     // KC_DEVROW=0: host rows + expand's own sync (A/B)
-    dev_row_off_ = dr && dr[0] == '0';
+    dev_row_off_ = !env_flag("KC_DEVROW", true);   // KC_DEVROW=0: host rows + expand's own sync (A/B)
     // fault injection for the failure-path tests: KC_FAULT=rank:level:stage
     // (stage 0 expand, 1 pack, 2 insert, 3 after the all-gather as if the
     // exchange buffers could not be grown) fails that rank's stage with -EIO
@@ -726,28 +685,22 @@ class Group {
     world_ = local_[0]->world();
     cfg_.spill_dir = nullptr;
     for (auto* s : local_) s->set_async_pack(true);
-    send_.assign(local_.size(), nullptr);
-    recv_.assign(local_.size(), nullptr);
-    send_cap_.assign(local_.size(), 0);
-    recv_cap_.assign(local_.size(), 0);
+    send_.resize(local_.size());
+    recv_.resize(local_.size());
     // device-driven narrow levels (shard_narrow.h); KC_SNARROW=0: every level
     // on the counted path; KC_SN_SLOT: records per peer slot
-    const char* sn = getenv("KC_SNARROW");
-    sn_on_ = !(sn && sn[0] == '0');
-    const char* sc = getenv("KC_SN_SLOT");
-    sn_cap_ = sc && atoi(sc) > 0 ? (uint32_t)atoi(sc) : SN_SLOT_DEFAULT;
+    sn_on_ = env_flag("KC_SNARROW", true);
+    const uint64_t sc = env_u64("KC_SN_SLOT");
+    sn_cap_ = sc ? (uint32_t)sc : SN_SLOT_DEFAULT;
     // KC_SOLO=0: a world-1 group runs the gather path too (A/B)
-    const char* so = getenv("KC_SOLO");
-    solo_off_ = so && so[0] == '0';
+    solo_off_ = !env_flag("KC_SOLO", true);
     // KC_SERIAL=1 (diagnostic): each local shard's stage is synchronised
     // before the next shard's launches, so emulated ranks' kernels never
     // overlap and a kernel trace attributes time per rank (Stream_Id)
-    const char* se = getenv("KC_SERIAL");
-    serial_ = se && se[0] == '1';
+    serial_ = env_flag("KC_SERIAL", false);
     // the deferred frontier on the counted levels (round 5); KC_SDEFER=0:
     // every insert materialises its new states (A/B)
-    const char* sd = getenv("KC_SDEFER");
-    defer_on_ = !(sd && sd[0] == '0');
+    defer_on_ = env_flag("KC_SDEFER", true);
   }
   // The narrow levels' buffers, allocated with the group (a failure here is
   // the caller's before any collective of a run).
@@ -768,11 +721,11 @@ class Group {
     return 0;
   }
   ~Group() {
-    if (h_fail_) (void)hipHostFree(h_fail_);
+    // (each rank's exchange buffers on its own device)
     for (size_t i = 0; i < local_.size(); ++i) {
       (void)hipSetDevice(local_[i]->device());
-      if (send_[i]) (void)hipFree(send_[i]);
-      if (recv_[i]) (void)hipFree(recv_[i]);
+      send_[i].reset();
+      recv_[i].reset();
     }
   }
   int run(kc_result* res);
@@ -805,16 +758,11 @@ class Group {
     *key = v;
     return 0;
   }
-  int buffer(std::vector<uint64_t*>& bufs, std::vector<uint64_t>& caps, size_t i, uint64_t bytes) {
-    if (bytes <= caps[i]) return 0;
+  int buffer(DeviceArray<uint8_t>& buf, size_t i, uint64_t bytes) {
+    if (bytes <= buf.cap) return 0;
     KC_HIP_TRY(hipSetDevice(local_[i]->device()));
     KC_HIP_TRY(hipStreamSynchronize(local_[i]->stream()));
-    if (bufs[i]) KC_HIP_TRY(hipFree(bufs[i]));
-    bufs[i] = nullptr;
-    const uint64_t nb = std::max<uint64_t>(bytes, 2 * caps[i]);
-    KC_HIP_TRY(hipMalloc(&bufs[i], nb));
-    caps[i] = nb;
-    return 0;
+    return buf.renew(std::max<uint64_t>(bytes, 2 * buf.cap));
   }
   // TLC order: the rank and local index of the state at position G of
   // `level` (every rank searches its sorted G values; one all-reduce)
@@ -847,14 +795,13 @@ class Group {
   std::unique_ptr<Comm> comm_;
   kc_model_config cfg_;
   int world_ = 1;
-  std::vector<uint64_t*> send_, recv_;
-  std::vector<uint64_t> send_cap_, recv_cap_;
+  std::vector<DeviceArray<uint8_t>> send_, recv_;   // (cap = bytes)
   std::vector<std::vector<uint64_t>> trace_;
   std::vector<uint64_t> sent_local_;   // records each local shard sent to other ranks
   uint64_t sent_ = 0;                  // all ranks (after run)
   uint64_t sn_levels_ = 0;             // levels run narrow (this run)
   bool dev_row_off_ = false;
-  uint64_t* h_fail_ = nullptr;         // pinned: failure words copied into device rows
+  PinnedArray<uint64_t> h_fail_;       // failure words copied into device rows
   int fault_rank_ = -1, fault_level_ = 0, fault_stage_ = 0;
   bool sn_on_ = true;
   bool solo_off_ = false;
@@ -914,7 +861,7 @@ int Group::run(kc_result* res) {
     // 1 is not expanded (max_levels = 1)
     if (!fail[i]) status_err[i] = local_[i]->init_error();
   }
-  if (!h_fail_) KC_HIP_TRY(hipHostMalloc(&h_fail_, 16 * 8));
+  KC_TRY(h_fail_.alloc(16));
   std::vector<uint64_t> widths;
   int level = 1;
   uint64_t err = NONE;
@@ -1178,24 +1125,25 @@ int Group::run(kc_result* res) {
       // a rank that failed here (expand_done above, or growing its buffers)
       // still takes part in the exchange: zeroed records, through the sink
       // if it has no buffers of the size
-      if (!fail[i]) note(i, buffer(send_, send_cap_, i, std::max<uint64_t>(ns, 1) * rb));
-      if (!fail[i]) note(i, buffer(recv_, recv_cap_, i, std::max<uint64_t>(nr, 1) * rb));
+      if (!fail[i]) note(i, buffer(send_[i], i, std::max<uint64_t>(ns, 1) * rb));
+      if (!fail[i]) note(i, buffer(recv_[i], i, std::max<uint64_t>(nr, 1) * rb));
       const bool grow_fault = !fail[i] && local_[i]->rank() == fault_rank_ && level == fault_level_ && fault_stage_ == 3;
       inject(i, level, 3);
-      if (fail[i] && (grow_fault || send_cap_[i] < std::max<uint64_t>(ns, 1) * rb ||
-                      recv_cap_[i] < std::max<uint64_t>(nr, 1) * rb))
+      if (fail[i] && (grow_fault || send_[i].cap < std::max<uint64_t>(ns, 1) * rb ||
+                      recv_[i].cap < std::max<uint64_t>(nr, 1) * rb))
         sunk[i] = 1;
       if (!fail[i]) note(i, hipSetDevice(local_[i]->device()) == hipSuccess ? 0 : -EIO);
       bool packed = false;
       if (!fail[i]) {
-        note(i, local_[i]->pack(send_[i]));
+        note(i, local_[i]->pack(send_[i].p));
         packed = !fail[i];
       }
       if (!packed && !sunk[i] && ns) note(i, hipMemsetAsync(send_[i], 0, ns * rb, local_[i]->stream()) == hipSuccess ? 0 : -EIO);
       ser(i);
       inject(i, level, 1);      // (a failure found after a complete pack)
     }
-    std::vector<void*> sv(send_.begin(), send_.end()), rv(recv_.begin(), recv_.end());
+    std::vector<void*> sv, rv;
+    for (size_t i = 0; i < local_.size(); ++i) sv.push_back(send_[i].p), rv.push_back(recv_[i].p);
     KC_TRY(comm_->all_to_all(sv, Mx, local_[0]->record_bytes(), rv, sunk));
     for (size_t i = 0; i < nl; ++i) {
       const int me = local_[i]->rank();
@@ -1204,7 +1152,7 @@ int Group::run(kc_result* res) {
       uint64_t n_new = 0, e2 = NONE;
       if (!fail[i]) note(i, hipSetDevice(local_[i]->device()) == hipSuccess ? 0 : -EIO);
       inject(i, level, 2);
-      if (!fail[i]) note(i, local_[i]->insert(recv_[i], nr, &n_new, &e2));
+      if (!fail[i]) note(i, local_[i]->insert(recv_[i].p, nr, &n_new, &e2));
       status_new[i] = fail[i] ? 0 : n_new;
       status_err[i] = fail[i] ? NONE : std::min(e1[i], e2);
     }
