@@ -28,6 +28,8 @@
 #include <string>
 #include <vector>
 
+#include "owned.h"
+
 namespace kc {
 
 namespace coldmix {
@@ -59,22 +61,22 @@ __host__ __device__ __forceinline__ uint64_t cold_unkey(uint64_t k) {
   return coldmix::unxorshift(z, 30);
 }
 
-// One sorted run of keys.
+// One sorted run of keys (move-only: it owns its buffers; its file is the
+// ColdSet's to unlink).
 struct ColdRun {
   uint64_t n = 0;                 // keys
-  uint64_t* host = nullptr;       // pinned host RAM (device-readable), or nullptr on disk
-  uint64_t host_cap = 0;          // keys the pinned buffer holds (pooled: >= n)
+  PinnedArray<uint64_t> host;     // pinned host RAM (device-readable; pooled: host.cap >= n), or empty on disk
   std::string path;               // the spill file when on disk
-  uint64_t* d_dir = nullptr;      // HBM: 2^dbits + 1 entries
+  DeviceArray<uint64_t> d_dir;    // HBM: 2^dbits + 1 entries
   int dbits = 1;
-  uint32_t* d_bloom = nullptr;    // HBM: nblocks x 16 words (nullptr = no filter)
+  DeviceArray<uint32_t> d_bloom;  // HBM: nblocks x 16 words (empty = no filter)
   uint64_t nblocks = 0;
   uint64_t meta_bytes = 0;        // HBM of dir + filter
-  uint64_t* d_keys = nullptr;     // HBM copy of the keys (the newest runs, as the budget allows)
+  DeviceArray<uint64_t> d_keys;   // HBM copy of the keys (the newest runs, as the budget allows)
   // disk runs: staging windows of wkeys keys; window w holds the keys in
   // [d_wkeys[w], d_wkeys[w + 1]) (d_wkeys[0] = 0, d_wkeys[nw] = ~0: HBM)
   uint64_t wkeys = 0, nw = 0;
-  uint64_t* d_wkeys = nullptr;
+  DeviceArray<uint64_t> d_wkeys;
   uint64_t bytes() const { return n * 8; }
 };
 
@@ -130,7 +132,6 @@ class ColdSet {
 
  private:
   int build_meta(ColdRun& r, const uint64_t* keys_dev_or_host, hipStream_t st);
-  void free_meta(ColdRun& r);
   int merge_last_two(hipStream_t st);
   int evict_oldest_host(hipStream_t st);
   int read_window(const ColdRun& r, uint64_t w0, uint64_t w1, uint64_t* dst);
@@ -145,9 +146,9 @@ class ColdSet {
   uint64_t cache_used_ = 0, cache_uploaded_ = 0;
   // pinned host buffers are pooled: pinning GBs of pages costs more than the
   // merges that use them
-  int pin_get(uint64_t keys, uint64_t** p, uint64_t* cap);
-  void pin_put(uint64_t* p, uint64_t cap);
-  std::vector<std::pair<uint64_t*, uint64_t>> pool_;
+  int pin_get(uint64_t keys, PinnedArray<uint64_t>& out);
+  void pin_put(PinnedArray<uint64_t>&& b);
+  std::vector<PinnedArray<uint64_t>> pool_;
   double t_pin_ = 0, t_merge_ = 0, t_meta_ = 0, t_evict_ = 0;
 
   Config cfg_;
@@ -156,13 +157,11 @@ class ColdSet {
   uint64_t merges_ = 0, merged_keys_ = 0, disk_written_ = 0, disk_read_ = 0, windows_skipped_ = 0;
   uint64_t merge_probes_ = 0;                  // (query set, run) pairs probed by the streaming merge
   uint64_t file_seq_ = 0, id_ = 0;
-  uint64_t* stage_[2] = {nullptr, nullptr};   // pinned staging windows (disk runs)
-  uint64_t stage_keys_ = 0;
-  hipEvent_t stage_ev_[2] = {nullptr, nullptr};
-  unsigned long long* d_stat_ = nullptr;       // [0] queries seen by filters, [1] passed
-  uint64_t* d_qa_ = nullptr;                   // disk runs: first query of each window
-  uint64_t* h_qa_ = nullptr;
-  uint64_t qa_cap_ = 0;
+  PinnedArray<uint64_t> stage_[2];             // staging windows (disk runs), of equal size
+  OwnedEvent stage_ev_[2];
+  DeviceArray<unsigned long long> d_stat_;     // [0] queries seen by filters, [1] passed
+  DeviceArray<uint64_t> d_qa_;                 // disk runs: first query of each window
+  PinnedArray<uint64_t> h_qa_;
 };
 
 }  // namespace kc

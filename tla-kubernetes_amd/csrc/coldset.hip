@@ -216,13 +216,12 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 
 // Best fit from the pool, else a fresh pinned buffer with 1/4 slack (the
 // size-tiered runs come in a few recurring sizes).
-int ColdSet::pin_get(uint64_t keys, uint64_t** p, uint64_t* cap) {
+int ColdSet::pin_get(uint64_t keys, PinnedArray<uint64_t>& out) {
   size_t best = pool_.size();
   for (size_t i = 0; i < pool_.size(); ++i)
-    if (pool_[i].second >= keys && (best == pool_.size() || pool_[i].second < pool_[best].second)) best = i;
+    if (pool_[i].cap >= keys && (best == pool_.size() || pool_[i].cap < pool_[best].cap)) best = i;
   if (best < pool_.size()) {
-    *p = pool_[best].first;
-    *cap = pool_[best].second;
+    out = std::move(pool_[best]);
     pool_.erase(pool_.begin() + best);
     return 0;
   }
@@ -231,33 +230,24 @@ int ColdSet::pin_get(uint64_t keys, uint64_t** p, uint64_t* cap) {
   // a few sizes, so freed buffers are reused instead of pinning new pages
   uint64_t c = 1ull << 16;
   while (c < keys) c *= 2;
-  KC_HIP_TRY(hipHostMalloc(p, c * 8));
-  *cap = c;
+  KC_TRY(out.alloc(c));
   t_pin_ += now_s() - t0;
   return 0;
 }
 // Back to the pool; the pool keeps its 6 largest buffers.
-void ColdSet::pin_put(uint64_t* p, uint64_t cap) {
-  if (!p) return;
-  pool_.push_back({p, cap});
-  std::sort(pool_.begin(), pool_.end(), [](const auto& a, const auto& b) { return a.second > b.second; });
-  while (pool_.size() > 6) {
-    (void)hipHostFree(pool_.back().first);
-    pool_.pop_back();
-  }
+void ColdSet::pin_put(PinnedArray<uint64_t>&& b) {
+  if (!b) return;
+  pool_.push_back(std::move(b));
+  std::sort(pool_.begin(), pool_.end(), [](const auto& x, const auto& y) { return x.cap > y.cap; });
+  while (pool_.size() > 6) pool_.pop_back();
 }
 
+// (an initialised set's members free themselves on its device; the files
+// are not theirs)
 ColdSet::~ColdSet() {
-  clear();
-  if (d_qa_) (void)hipFree(d_qa_);
-  if (h_qa_) (void)hipHostFree(h_qa_);
-  for (int s = 0; s < 2; ++s) {
-    if (stage_[s]) (void)hipHostFree(stage_[s]);
-    if (stage_ev_[s]) (void)hipEventDestroy(stage_ev_[s]);
-  }
-  if (d_stat_) (void)hipFree(d_stat_);
-  for (auto& b : pool_) (void)hipHostFree(b.first);
-  pool_.clear();
+  if (id_) (void)hipSetDevice(cfg_.device);
+  for (const auto& r : runs_)
+    if (!r.path.empty()) unlink(r.path.c_str());
 }
 
 int ColdSet::init(const Config& c) {
@@ -270,29 +260,15 @@ int ColdSet::init(const Config& c) {
   if (md) cfg_.merge_div = atoi(md);
   id_ = ++ids;
   if (!d_stat_) {
-    KC_HIP_TRY(hipMalloc(&d_stat_, 16));
+    KC_TRY(d_stat_.alloc(2));
     KC_HIP_TRY(hipMemset(d_stat_, 0, 16));
   }
   return 0;
 }
 
-void ColdSet::free_meta(ColdRun& r) {
-  if (r.d_wkeys) (void)hipFree(r.d_wkeys);
-  r.d_wkeys = nullptr;
-  r.nw = r.wkeys = 0;
-  if (r.d_dir) (void)hipFree(r.d_dir);
-  if (r.d_bloom) (void)hipFree(r.d_bloom);
-  meta_used_ -= r.meta_bytes;
-  r.d_dir = nullptr;
-  r.d_bloom = nullptr;
-  r.meta_bytes = 0;
-  r.nblocks = 0;
-}
-
 void ColdSet::uncache(ColdRun& r) {
   if (!r.d_keys) return;
-  (void)hipFree(r.d_keys);
-  r.d_keys = nullptr;
+  r.d_keys.reset();
   cache_used_ -= r.bytes();
 }
 
@@ -311,8 +287,7 @@ int ColdSet::recache(hipStream_t st) {
     ColdRun& r = runs_[k];
     if (r.d_keys || r.n == 0) continue;
     if (cfg_.meta_hbm_bytes && meta_used_ + cache_used_ + r.bytes() > cfg_.meta_hbm_bytes) break;
-    if (hipMalloc(&r.d_keys, r.bytes()) != hipSuccess) {
-      r.d_keys = nullptr;
+    if (r.d_keys.alloc(r.n) < 0) {
       (void)hipGetLastError();
       break;
     }
@@ -335,12 +310,14 @@ int ColdSet::recache(hipStream_t st) {
   return 0;
 }
 
+// Out of the accounting; the pinned buffer goes back to the pool, the file
+// and the rest of what the run owns go.
 void ColdSet::free_run(ColdRun& r) {
   uncache(r);
-  free_meta(r);
+  meta_used_ -= r.meta_bytes;
   if (r.host) {
-    pin_put(r.host, r.host_cap);
     host_used_ -= r.bytes();
+    pin_put(std::move(r.host));
   }
   if (!r.path.empty()) {
     unlink(r.path.c_str());
@@ -376,7 +353,7 @@ int ColdSet::build_meta(ColdRun& r, const uint64_t* keys, hipStream_t st) {
               (unsigned long long)cfg_.meta_hbm_bytes);
     return -ENOMEM;
   }
-  KC_HIP_TRY(hipMalloc(&r.d_dir, dir_bytes));
+  KC_TRY(r.d_dir.alloc((1ull << dbits) + 1));
   r.dbits = dbits;
   r.meta_bytes = dir_bytes;
   meta_used_ += dir_bytes;
@@ -389,7 +366,7 @@ int ColdSet::build_meta(ColdRun& r, const uint64_t* keys, hipStream_t st) {
   if (bits >= 4 && r.n) {
     r.nblocks = std::max<uint64_t>(1, r.n * bits / 512);
     const uint64_t fb = r.nblocks * 64;
-    KC_HIP_TRY(hipMalloc(&r.d_bloom, fb));
+    KC_TRY(r.d_bloom.alloc(r.nblocks * 16));
     KC_HIP_TRY(hipMemsetAsync(r.d_bloom, 0, fb, st));
     r.meta_bytes += fb;
     meta_used_ += fb;
@@ -405,13 +382,13 @@ int ColdSet::add_run(const uint64_t* d_sorted, uint64_t n, hipStream_t st) {
   if (n == 0) return 0;
   ColdRun r;
   r.n = n;
-  KC_TRY(pin_get(n, &r.host, &r.host_cap));
+  KC_TRY(pin_get(n, r.host));
   host_used_ += r.bytes();
   keys_ += n;
   const double t0 = now_s();
   KC_HIP_TRY(hipMemcpyAsync(r.host, d_sorted, n * 8, hipMemcpyDeviceToHost, st));
   const int rc = build_meta(r, d_sorted, st);
-  runs_.push_back(r);                   // owned (and freed) by runs_ from here on
+  runs_.push_back(std::move(r));        // (in the accounting: runs_ frees it from here on)
   KC_TRY(rc);
   KC_HIP_TRY(hipStreamSynchronize(st));
   t_meta_ += now_s() - t0;
@@ -424,7 +401,7 @@ int ColdSet::add_run(const uint64_t* d_sorted, uint64_t n, hipStream_t st) {
   }
   while (cfg_.host_bytes && host_used_ > cfg_.host_bytes) {
     bool any = false;
-    for (const auto& x : runs_) any |= x.host != nullptr;
+    for (const auto& x : runs_) any |= x.host.p != nullptr;
     if (!any) break;
     KC_TRY(evict_oldest_host(st));
   }
@@ -436,7 +413,7 @@ int ColdSet::merge_last_two(hipStream_t st) {
   ColdRun& b = runs_.back();
   ColdRun c;
   c.n = a.n + b.n;
-  KC_TRY(pin_get(c.n, &c.host, &c.host_cap));
+  KC_TRY(pin_get(c.n, c.host));
   host_used_ += c.bytes();
   const double t0 = now_s();
   // the key space cut into T equal ranges, each merged by its own thread
@@ -448,8 +425,8 @@ int ColdSet::merge_last_two(hipStream_t st) {
   ib[T] = b.n;
   for (int t = 1; t < T; ++t) {
     const uint64_t s = (uint64_t)(((unsigned __int128)t << 64) / (unsigned)T);
-    ia[t] = std::lower_bound(a.host, a.host + a.n, s) - a.host;
-    ib[t] = std::lower_bound(b.host, b.host + b.n, s) - b.host;
+    ia[t] = std::lower_bound(a.host.p, a.host.p + a.n, s) - a.host.p;
+    ib[t] = std::lower_bound(b.host.p, b.host.p + b.n, s) - b.host.p;
   }
   const uint64_t *pa = a.host, *pb = b.host;
   uint64_t* pc = c.host;
@@ -462,7 +439,7 @@ int ColdSet::merge_last_two(hipStream_t st) {
     work(0);
     for (auto& x : th) x.join();
   } catch (...) {
-    pin_put(c.host, c.host_cap);
+    pin_put(std::move(c.host));
     host_used_ -= c.bytes();
     set_error("seen-set: cannot start merge threads");
     return -ENOMEM;
@@ -478,7 +455,7 @@ int ColdSet::merge_last_two(hipStream_t st) {
   runs_.pop_back();
   keys_ += c.n;
   const int rc = build_meta(c, c.host, st);
-  runs_.push_back(c);
+  runs_.push_back(std::move(c));
   KC_TRY(rc);
   KC_HIP_TRY(hipStreamSynchronize(st));
   t_meta_ += now_s() - t1;
@@ -506,7 +483,7 @@ int ColdSet::evict_oldest_host(hipStream_t st) {
       set_error("seen-set: cannot create spill file %s", path.c_str());
       return -EIO;
     }
-    const char* p = reinterpret_cast<const char*>(r.host);
+    const char* p = reinterpret_cast<const char*>(r.host.p);
     uint64_t left = r.bytes(), off = 0;
     while (left) {
       const ssize_t w = pwrite(fd, p + off, std::min<uint64_t>(left, 1ull << 30), (off_t)off);
@@ -531,11 +508,9 @@ int ColdSet::evict_oldest_host(hipStream_t st) {
     wk[0] = 0;
     for (uint64_t w = 1; w < r.nw; ++w) wk[w] = r.host[w * r.wkeys];
     wk[r.nw] = ~0ull;
-    KC_HIP_TRY(hipMalloc(&r.d_wkeys, (r.nw + 1) * 8));
+    KC_TRY(r.d_wkeys.alloc(r.nw + 1));
     KC_HIP_TRY(hipMemcpy(r.d_wkeys, wk.data(), (r.nw + 1) * 8, hipMemcpyHostToDevice));
-    pin_put(r.host, r.host_cap);
-    r.host = nullptr;
-    r.host_cap = 0;
+    pin_put(std::move(r.host));
     host_used_ -= r.bytes();
     r.path = path;
     disk_used_ += r.bytes();
@@ -547,17 +522,13 @@ int ColdSet::evict_oldest_host(hipStream_t st) {
 }
 
 int ColdSet::staging(uint64_t keys) {
-  if (keys <= stage_keys_) return 0;
+  if (keys <= std::min(stage_[0].cap, stage_[1].cap)) return 0;
+  stage_[0].reset();      // (both go before either comes)
+  stage_[1].reset();
   for (int s = 0; s < 2; ++s) {
-    if (stage_[s]) (void)hipHostFree(stage_[s]);
-    stage_[s] = nullptr;
+    KC_TRY(stage_[s].alloc(keys));
+    KC_TRY(stage_ev_[s].create(hipEventDisableTiming));
   }
-  stage_keys_ = 0;
-  for (int s = 0; s < 2; ++s) {
-    KC_HIP_TRY(hipHostMalloc(&stage_[s], keys * 8));
-    if (!stage_ev_[s]) KC_HIP_TRY(hipEventCreateWithFlags(&stage_ev_[s], hipEventDisableTiming));
-  }
-  stage_keys_ = keys;
   return 0;
 }
 
@@ -597,7 +568,7 @@ int ColdSet::probe(const uint64_t* d_q, uint64_t m, uint8_t* d_found, unsigned l
     }
     if (r.d_keys || r.host) {         // HBM copy, else the pinned host run read over the link
       hipLaunchKernelGGL(k_cold_probe, dim3(grid_of(m)), dim3(256), 0, st, d_q, m, d_found,
-                         r.d_keys ? r.d_keys : r.host, 0ull, r.n, r.d_dir, r.dbits, r.d_bloom, r.nblocks, d_hits,
+                         r.d_keys ? r.d_keys.p : r.host.p, 0ull, r.n, r.d_dir, r.dbits, r.d_bloom, r.nblocks, d_hits,
                          d_stat_);
       continue;
     }
@@ -605,15 +576,9 @@ int ColdSet::probe(const uint64_t* d_q, uint64_t m, uint8_t* d_found, unsigned l
     // through two pinned buffers (read one while the GPU probes the other);
     // each window's launch covers just its queries
     KC_TRY(staging(r.wkeys));
-    if (qa_cap_ < r.nw + 1) {
-      if (d_qa_) (void)hipFree(d_qa_);
-      if (h_qa_) (void)hipHostFree(h_qa_);
-      d_qa_ = nullptr;
-      h_qa_ = nullptr;
-      qa_cap_ = 0;
-      KC_HIP_TRY(hipMalloc(&d_qa_, (r.nw + 1) * 8));
-      KC_HIP_TRY(hipHostMalloc(&h_qa_, (r.nw + 1) * 8));
-      qa_cap_ = r.nw + 1;
+    if (std::min(d_qa_.cap, h_qa_.cap) < r.nw + 1) {
+      KC_TRY(d_qa_.renew(r.nw + 1));
+      KC_TRY(h_qa_.renew(r.nw + 1));
     }
     hipLaunchKernelGGL(k_window_ranges, dim3(grid_of(r.nw + 1)), dim3(256), 0, st, d_q, m, r.d_wkeys, r.nw, d_qa_);
     KC_HIP_TRY(hipMemcpyAsync(h_qa_, d_qa_, (r.nw + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -678,7 +643,7 @@ int ColdSet::all_keys(std::vector<uint64_t>& out) {
   for (const auto& r : runs_) {
     const size_t at = out.size();
     if (r.host) {
-      out.insert(out.end(), r.host, r.host + r.n);
+      out.insert(out.end(), r.host.p, r.host.p + r.n);
     } else {
       buf.resize(r.n);
       KC_TRY(read_window(r, 0, r.n, buf.data()));

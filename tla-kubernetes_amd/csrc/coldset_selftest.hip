@@ -23,8 +23,8 @@ namespace {
 constexpr uint64_t kColdTestMax = 1ull << 21;     // keys per add, queries per probe
 
 struct ColdHarness {
+  OwnedStream st;                   // (before the set: destroyed after its buffers)
   ColdSet cs;
-  hipStream_t st = nullptr;
   bool failed = false;              // an add_run failed: no probe / all_keys until clear
 };
 
@@ -84,7 +84,7 @@ int kc_coldset_create(uint64_t meta_hbm_bytes, uint64_t host_bytes, const char* 
   c.cache_keys = cache_keys != 0;
   c.merge_div = merge_div;
   int rc = h->cs.init(c);
-  if (rc == 0 && hipStreamCreate(&h->st) != hipSuccess) {
+  if (rc == 0 && h->st.create(hipStreamDefault) < 0) {
     set_error("kc_coldset_create: cannot create a stream");
     rc = -EIO;
   }
@@ -112,9 +112,9 @@ int kc_coldset_add_run(void* hv, const uint64_t* keys, uint64_t n) {
     return -EINVAL;
   }
   DevBuf d;
-  KC_HIP_TRY(hipMalloc(&d.p, n * 8));
+  KC_TRY(d.alloc(n * 8));
   KC_HIP_TRY(hipMemcpy(d.p, keys, n * 8, hipMemcpyHostToDevice));
-  const int rc = h->cs.add_run(static_cast<const uint64_t*>(d.p), n, h->st);
+  const int rc = h->cs.add_run(d.as<const uint64_t>(), n, h->st);
   (void)hipStreamSynchronize(h->st);       // (a failed add may have left its copy in flight)
   if (rc < 0) h->failed = true;
   return rc;
@@ -136,14 +136,13 @@ int kc_coldset_probe(void* hv, const uint64_t* q, uint64_t m, uint8_t* found, ui
     return -EINVAL;
   }
   DevBuf dq, df, dh;
-  KC_HIP_TRY(hipMalloc(&dq.p, m * 8));
-  KC_HIP_TRY(hipMalloc(&df.p, m));
-  KC_HIP_TRY(hipMalloc(&dh.p, 8));
+  KC_TRY(dq.alloc(m * 8));
+  KC_TRY(df.alloc(m));
+  KC_TRY(dh.alloc(8));
   KC_HIP_TRY(hipMemcpy(dq.p, q, m * 8, hipMemcpyHostToDevice));
   KC_HIP_TRY(hipMemcpy(df.p, found, m, hipMemcpyHostToDevice));
   KC_HIP_TRY(hipMemcpy(dh.p, hits, 8, hipMemcpyHostToDevice));
-  const int rc = h->cs.probe(static_cast<const uint64_t*>(dq.p), m, static_cast<uint8_t*>(df.p),
-                             static_cast<unsigned long long*>(dh.p), h->st);
+  const int rc = h->cs.probe(dq.as<const uint64_t>(), m, df.p, dh.as<unsigned long long>(), h->st);
   KC_HIP_TRY(hipStreamSynchronize(h->st));
   KC_TRY(rc);
   KC_HIP_TRY(hipMemcpy(found, df.p, m, hipMemcpyDeviceToHost));
@@ -198,7 +197,6 @@ void kc_coldset_destroy(void* hv) {
   ColdHarness* h = static_cast<ColdHarness*>(hv);
   if (!h) return;
   h->cs.clear();
-  if (h->st) (void)hipStreamDestroy(h->st);
   delete h;
 }
 
@@ -213,11 +211,11 @@ int kc_cold_key_selftest(const uint64_t* in, uint64_t* out, uint64_t n, int unke
   }
   KC_TRY(have_device("kc_cold_key_selftest"));
   DevBuf di, dout;
-  KC_HIP_TRY(hipMalloc(&di.p, n * 8));
-  KC_HIP_TRY(hipMalloc(&dout.p, n * 8));
+  KC_TRY(di.alloc(n * 8));
+  KC_TRY(dout.alloc(n * 8));
   KC_HIP_TRY(hipMemcpy(di.p, in, n * 8, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_cold_key_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr,
-                     static_cast<const uint64_t*>(di.p), static_cast<uint64_t*>(dout.p), n, unkey);
+                     di.as<const uint64_t>(), dout.as<uint64_t>(), n, unkey);
   KC_HIP_TRY(hipGetLastError());
   KC_HIP_TRY(hipDeviceSynchronize());
   KC_HIP_TRY(hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost));

@@ -89,7 +89,7 @@ int sync_launch() {
 
 // Counters with err_key = ~0 (none) and the chunk's base.
 int make_counters(DevBuf& c, uint64_t chunk_base) {
-  KC_HIP_TRY(hipMalloc(&c.p, sizeof(Counters)));
+  KC_TRY(c.alloc(sizeof(Counters)));
   KC_HIP_TRY(hipMemset(c.p, 0, sizeof(Counters)));
   unsigned long long head[2] = {~0ull, chunk_base};
   KC_HIP_TRY(hipMemcpy(c.p, head, sizeof(head), hipMemcpyHostToDevice));
@@ -410,13 +410,6 @@ int run_materialize(const Flags& f, const uint64_t* par, uint64_t npar, const ui
 }
 
 // ---------------------------------------------------------------- parent chain
-struct HostBuf {
-  uint64_t* p = nullptr;
-  ~HostBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-};
-
 // kind 5.  par = [g, cap]; a = parent[na] (each below na, or ~0), b = ord[na]
 // (bytes), g < na.  out = pinned host memory, as in the engine: fore guards,
 // the length word, then cap chain words at least; uploaded as given.
@@ -431,10 +424,10 @@ int run_parent_chain(const uint64_t* par, uint64_t npar, const uint64_t* a, uint
     if ((a[i] >= na && a[i] != ~0ull) || b[i] > 0xff) return bad("parent_chain: a parent outside the states");
   KC_TRY(need_device());   // (the input is valid: -EINVAL needs no GPU)
   DevBuf pa, od;
-  HostBuf h;
+  PinnedArray<uint64_t> h;
   KC_TRY(upload(pa, a, na * 8));
   KC_TRY(upload_as<uint8_t>(od, b, na));
-  KC_HIP_TRY(hipHostMalloc(&h.p, nout * 8));
+  KC_TRY(h.alloc(nout));
   memcpy(h.p, out, nout * 8);
   hipLaunchKernelGGL(k_parent_chain, dim3(1), dim3(64), 0, nullptr, pa.as<const unsigned long long>(),
                      od.as<const uint8_t>(), g, h.p + FORE + 1, (uint32_t)cap, h.p + FORE);

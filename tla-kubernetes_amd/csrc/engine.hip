@@ -227,7 +227,7 @@ class EngineT final : public EngineBase {
     cs_.compact = first_claim_ && env_flag("KC_CLAIM_COMPACT", true);
     chunk_scan_ = env_flag("KC_CHUNK_SCAN", true);
   }
-  ~EngineT() override { release(); }
+  ~EngineT() override { (void)hipSetDevice(cfg_.device); }   // (the members free themselves on it)
 
   int state_words() const override { return M::W; }
   int tuple_words() const override { return M::TUPLE_WORDS; }
@@ -243,7 +243,7 @@ class EngineT final : public EngineBase {
       return -EINVAL;
     }
     KC_HIP_TRY(hipSetDevice(cfg_.device));
-    KC_HIP_TRY(hipStreamCreateWithFlags(&st_.s, hipStreamNonBlocking));
+    KC_TRY(st_.create(hipStreamNonBlocking));
     KC_TRY(d_ctr_.alloc(1));
     KC_TRY(h_ctr_.alloc(1));
     KC_TRY(d_ns_.alloc(1));
@@ -921,11 +921,9 @@ class EngineT final : public EngineBase {
     // level cost the NP=2 check 6 ms and Model_1 4 ms of host/queue time)
     if (timing_ == 1 || (timing_ == 2 && (k == KK_EXPAND || k == KK_NARROW))) {
       if (ev_used_ + 2 > ev_pool_.size()) {
-        hipEvent_t a, b;
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
-        ev_pool_.push_back(a);
-        ev_pool_.push_back(b);
+        ev_pool_.resize(ev_used_ + 2);
+        (void)ev_pool_[ev_used_].create();
+        (void)ev_pool_[ev_used_ + 1].create();
       }
       hipEvent_t a = ev_pool_[ev_used_], b = ev_pool_[ev_used_ + 1];
       (void)hipEventRecord(a, st_);
@@ -1108,15 +1106,6 @@ class EngineT final : public EngineBase {
       res->frontier_peak_hbm_bytes = qs.peak_hbm_bytes;
     }
     res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0_).count();
-  }
-
-  // What is not a buffer.  The buffers free themselves after this, with the
-  // device still current; the stream (st_, declared before them) goes last.
-  void release() {
-    (void)hipSetDevice(cfg_.device);
-    cs_.release();
-    q_.reset();
-    for (auto& e : ev_pool_) (void)hipEventDestroy(e);
   }
 
   // One launch of k_narrow from the host loop's state; on return the
@@ -1790,7 +1779,7 @@ class EngineT final : public EngineBase {
   PinnedArray<Counters> h_ctr_;
   PinnedArray<uint64_t> h_chain_;      // [0] length, then the parent chain (k_parent_chain)
   std::chrono::steady_clock::time_point t0_;   // the run's start
-  std::vector<hipEvent_t> ev_pool_;
+  std::vector<OwnedEvent> ev_pool_;
   std::vector<int> ev_kind_;
   size_t ev_used_ = 0;
   std::vector<State> init_states_, trace_, captured_;

@@ -276,7 +276,7 @@ struct SeenSpill {
     if (c) {
       // sort in place, borrowing the hot table (cleared right after) as the
       // alternate buffer and temporary storage
-      uint64_t* alt = reinterpret_cast<uint64_t*>(cs.t);
+      uint64_t* alt = reinterpret_cast<uint64_t*>(cs.t.p);
       const uint64_t tab = cs.nslots * sizeof(ClaimEntry);
       const uint64_t off = (c * 8 + 255) / 256 * 256;
       hipcub::DoubleBuffer<uint64_t> kb(keys, alt);
@@ -287,7 +287,7 @@ struct SeenSpill {
                   (unsigned long long)tab);
         return -ENOMEM;
       }
-      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(reinterpret_cast<uint8_t*>(cs.t) + off, tb, kb, (int)c, 0, 64, st));
+      KC_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(reinterpret_cast<uint8_t*>(cs.t.p) + off, tb, kb, (int)c, 0, 64, st));
       KC_TRY(cold.add_run(kb.Current(), c, st));
     }
     KC_TRY(cs.clear(st));

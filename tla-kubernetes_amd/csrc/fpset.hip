@@ -14,7 +14,6 @@
 
 #include "../../include/kubecheck.h"
 #include "engine_kernels.h"
-#include "engine_util.h"
 #include "fpset_host.h"
 #include "kc_common.h"
 
@@ -56,31 +55,20 @@ void launch_fpset_insert_list(const uint64_t* d_fps, uint64_t n, const DevFpset&
 }
 
 int DevFpset::init(uint64_t min_slots, hipStream_t st) {
-  release();
   nbuckets = (min_slots + 7) / 8;
   if (nbuckets < 8) nbuckets = 8;
-  KC_HIP_TRY(hipMalloc(&slots, nbuckets * 64));
+  count = 0;
+  KC_TRY(slots.renew(nbuckets * 8));
   KC_HIP_TRY(hipMemsetAsync(slots, 0, nbuckets * 64, st));
-  KC_HIP_TRY(hipMalloc(&d_fail, sizeof(unsigned long long)));
-  count = 0;
-  return 0;
-}
-
-void DevFpset::release() {
-  if (slots) (void)hipFree(slots);
-  if (d_fail) (void)hipFree(d_fail);
-  slots = nullptr;
-  d_fail = nullptr;
-  nbuckets = 0;
-  count = 0;
+  return d_fail.renew(1);
 }
 
 int DevFpset::reserve(uint64_t extra, hipStream_t st) {
   if ((count + extra) * 4 <= capacity() * 3) return 0;
   uint64_t nb = nbuckets;
   while ((count + extra) * 4 > nb * 8 * 2) nb *= 2;  // land at <= 50% load
-  unsigned long long* ns = nullptr;
-  KC_HIP_TRY(hipMalloc(&ns, nb * 64));
+  DeviceArray<unsigned long long> ns;   // (swapped in once the rehash reported no failure)
+  KC_TRY(ns.alloc(nb * 8));
   KC_HIP_TRY(hipMemsetAsync(ns, 0, nb * 64, st));
   KC_HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), st));
   const uint64_t old_slots = capacity();
@@ -90,12 +78,10 @@ int DevFpset::reserve(uint64_t extra, hipStream_t st) {
   KC_HIP_TRY(hipMemcpyAsync(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost, st));
   KC_HIP_TRY(hipStreamSynchronize(st));
   if (fail) {
-    (void)hipFree(ns);
     set_error("fpset rehash failed (%llu)", fail);
     return -ENOMEM;
   }
-  KC_HIP_TRY(hipFree(slots));
-  slots = ns;
+  slots.swap(ns);
   nbuckets = nb;
   return 0;
 }
@@ -196,13 +182,11 @@ void launch_claimset_insert_list(const uint64_t* d_fps, uint64_t n, const DevCla
 }
 
 int DevClaimSet::init(uint64_t min_slots, hipStream_t st) {
-  release();
   nslots = min_slots < 64 ? 64 : min_slots;
-  KC_HIP_TRY(hipMalloc(&t, nslots * slot_bytes()));
-  KC_HIP_TRY(hipMemsetAsync(t, 0, nslots * slot_bytes(), st));
-  KC_HIP_TRY(hipMalloc(&d_fail, sizeof(unsigned long long)));
   count = 0;
-  return 0;
+  KC_TRY(t.renew(units(nslots)));
+  KC_HIP_TRY(hipMemsetAsync(t, 0, nslots * slot_bytes(), st));
+  return d_fail.renew(1);
 }
 
 // (an 8,192-workgroup grid-stride clear kernel: 6.9 TB/s on the 64 GiB NP=2
@@ -220,15 +204,6 @@ int DevClaimSet::clear(hipStream_t st) {
   return 0;
 }
 
-void DevClaimSet::release() {
-  if (t) (void)hipFree(t);
-  if (d_fail) (void)hipFree(d_fail);
-  t = nullptr;
-  d_fail = nullptr;
-  nslots = 0;
-  count = 0;
-}
-
 // Linear probing: every extra probe of a chain is a dependent load the
 // claim kernel waits for, so the load factor is paid in k_claim time (NP=2:
 // 64 GiB at 17% load runs the check 2.3% faster than 32 GiB at 35%, its
@@ -244,18 +219,17 @@ int DevClaimSet::reserve(uint64_t extra, hipStream_t st) {
   uint64_t ns = nslots, ns_min = nslots;
   while (need * (ld + 1) > ns) ns *= 2;
   while (need * 2 > ns_min) ns_min *= 2;
-  ClaimEntry* nt = nullptr;
-  if (hipMalloc(&nt, ns * slot_bytes()) != hipSuccess) {
+  DeviceArray<ClaimEntry> nt;   // (swapped in once the rehash reported no failure)
+  if (nt.alloc(units(ns)) < 0) {
     (void)hipGetLastError();
-    nt = nullptr;
     ns = ns_min;
     if (ns == nslots) return 0;                    // (still <= 1/2 after this batch)
-    KC_HIP_TRY(hipMalloc(&nt, ns * slot_bytes()));
+    KC_TRY(nt.alloc(units(ns)));
   }
   KC_HIP_TRY(hipMemsetAsync(nt, 0, ns * slot_bytes(), st));
   KC_HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), st));
   if (compact)
-    launch_fpslots_rehash(words(), nslots, reinterpret_cast<unsigned long long*>(nt), ns, d_fail, st);
+    launch_fpslots_rehash(words(), nslots, reinterpret_cast<unsigned long long*>(nt.p), ns, d_fail, st);
   else
     launch_claimset_rehash(t, nslots, nt, ns, d_fail, st);
   KC_HIP_TRY(hipGetLastError());
@@ -263,29 +237,17 @@ int DevClaimSet::reserve(uint64_t extra, hipStream_t st) {
   KC_HIP_TRY(hipMemcpyAsync(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost, st));
   KC_HIP_TRY(hipStreamSynchronize(st));
   if (fail) {
-    (void)hipFree(nt);
     set_error("claimset rehash failed (%llu)", fail);
     return -ENOMEM;
   }
-  KC_HIP_TRY(hipFree(t));
-  t = nt;
+  t.swap(nt);
   nslots = ns;
   return 0;
 }
 
 int DevBatchTable::ensure(uint64_t entries, hipStream_t st) {
   (void)st;
-  if (entries <= cap) return 0;
-  release();
-  KC_HIP_TRY(hipMalloc(&t, entries * sizeof(BatchEntry)));
-  cap = entries;
-  return 0;
-}
-
-void DevBatchTable::release() {
-  if (t) (void)hipFree(t);
-  t = nullptr;
-  cap = 0;
+  return entries <= t.cap ? 0 : t.renew(entries);
 }
 
 // --------------------------------------------------------------- kernels
@@ -550,16 +512,15 @@ struct Combiner {
 
 struct kc_fpset {
   int device = 0;
-  hipStream_t stream = nullptr;
+  OwnedStream stream;   // (first: destroyed after every buffer below)
   DevFpset fs;
   DevBatchTable bt;
-  uint64_t* d_fps = nullptr;
-  uint8_t* d_seen = nullptr;
-  uint64_t stage_cap = 0;
-  unsigned long long* d_stats = nullptr;  // STAT_ROWS rows of [new, full, found, -]
+  DeviceArray<uint64_t> d_fps;   // staging: d_fps.cap fingerprints and as many answers
+  DeviceArray<uint8_t> d_seen;
+  DeviceArray<unsigned long long> d_stats;  // STAT_ROWS rows of [new, full, found, -]
   DeviceArray<uint32_t> part_cnt, part_off;   // owner partition scratch
   DeviceArray<uint8_t> scan_tmp;
-  uint8_t* h_small = nullptr;   // pinned: SMALL_MAX fps, SMALL_MAX answers, 2 counts (k_small_round)
+  PinnedArray<uint8_t> h_small;   // SMALL_MAX fps, SMALL_MAX answers, 2 counts (k_small_round)
   std::mutex mu;
   Combiner comb;
 };
@@ -568,11 +529,11 @@ struct kc_fpset {
 static int small_round(kc_fpset* s, const uint64_t* fps, size_t n, int op, uint8_t* seen) {
   std::lock_guard<std::mutex> g(s->mu);
   KC_HIP_TRY(hipSetDevice(s->device));
-  if (!s->h_small) KC_HIP_TRY(hipHostMalloc(&s->h_small, SMALL_MAX * 9 + 64));
+  KC_TRY(s->h_small.alloc(SMALL_MAX * 9 + 64));
   if (op == 0) KC_TRY(s->fs.reserve(n, s->stream));
-  uint64_t* hf = reinterpret_cast<uint64_t*>(s->h_small);
-  uint8_t* hs = s->h_small + SMALL_MAX * 8;
-  unsigned long long* hc = reinterpret_cast<unsigned long long*>(s->h_small + SMALL_MAX * 9 + 8 - (SMALL_MAX * 9) % 8);
+  uint64_t* hf = reinterpret_cast<uint64_t*>(s->h_small.p);
+  uint8_t* hs = s->h_small.p + SMALL_MAX * 8;
+  unsigned long long* hc = reinterpret_cast<unsigned long long*>(s->h_small.p + SMALL_MAX * 9 + 8 - (SMALL_MAX * 9) % 8);
   memcpy(hf, fps, n * 8);
   hipLaunchKernelGGL(k_small_round, dim3(1), dim3(SMALL_MAX), 0, s->stream, hf, (uint32_t)n, op, s->fs.slots,
                      s->fs.nbuckets, hs, hc);
@@ -600,17 +561,10 @@ static int read_stats(kc_fpset* s, hipStream_t st, unsigned long long out[4]) {
 }
 
 static int stage(kc_fpset* s, uint64_t n) {
-  if (n <= s->stage_cap) return 0;
-  if (s->d_fps) (void)hipFree(s->d_fps);
-  if (s->d_seen) (void)hipFree(s->d_seen);
-  s->d_fps = nullptr;
-  s->d_seen = nullptr;
-  s->stage_cap = 0;
+  if (n <= std::min(s->d_fps.cap, s->d_seen.cap)) return 0;
   const uint64_t cap = next_pow2(n);
-  KC_HIP_TRY(hipMalloc(&s->d_fps, cap * 8));
-  KC_HIP_TRY(hipMalloc(&s->d_seen, cap));
-  s->stage_cap = cap;
-  return 0;
+  KC_TRY(s->d_fps.renew(cap));
+  return s->d_seen.renew(cap);
 }
 
 static int put_dev(kc_fpset* s, uint64_t* fps, size_t n, uint8_t* seen, hipStream_t st,
@@ -656,9 +610,9 @@ int kc_fpset_create(uint64_t capacity_fps, int device, kc_fpset** out) {
   // a BLOCKING stream: it orders with the legacy default stream, which is
   // where a caller's NULL-stream work (and torch's default stream) runs, so
   // a *_dev call without a stream sees the caller's earlier writes
-  if (hipStreamCreate(&s->stream) != hipSuccess) rc = -EIO;
+  if (s->stream.create(hipStreamDefault) < 0) rc = -EIO;
   if (!rc) rc = s->fs.init(capacity_fps * 4 / 3 + 8, s->stream);
-  if (!rc && hipMalloc(&s->d_stats, STAT_BYTES) != hipSuccess) rc = -ENOMEM;
+  if (!rc && s->d_stats.alloc(STAT_ROWS * 8) < 0) rc = -ENOMEM;
   if (!rc && hipStreamSynchronize(s->stream) != hipSuccess) rc = -EIO;
   if (rc) { kc_fpset_destroy(s); if (rc == -EIO) set_error("kc_fpset_create: HIP failure"); return rc; }
   *out = s;
@@ -668,16 +622,6 @@ int kc_fpset_create(uint64_t capacity_fps, int device, kc_fpset** out) {
 void kc_fpset_destroy(kc_fpset* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  s->fs.release();
-  s->bt.release();
-  if (s->d_fps) (void)hipFree(s->d_fps);
-  if (s->d_seen) (void)hipFree(s->d_seen);
-  if (s->d_stats) (void)hipFree(s->d_stats);
-  if (s->h_small) (void)hipHostFree(s->h_small);
-  s->part_cnt.reset();
-  s->part_off.reset();
-  s->scan_tmp.reset();
-  if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
 
@@ -742,14 +686,13 @@ int kc_fpset_check_fps(kc_fpset* s, uint64_t* min_gap_out, double* prob_out) {
   KC_HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   const uint64_t nslots = s->fs.capacity();
-  unsigned long long *d_a = nullptr, *d_b = nullptr, *d_n = nullptr;
-  void* tmp = nullptr;
+  DeviceArray<unsigned long long> d_a, d_b, d_n;
+  DeviceArray<uint8_t> tmp;
   size_t tmp_bytes = 0;
   int rc = 0;
   unsigned long long n = 0, gap = ~0ull;
   const uint64_t cnt = s->fs.count ? s->fs.count : 1;
-  if (hipMalloc(&d_a, cnt * 8) != hipSuccess || hipMalloc(&d_b, cnt * 8) != hipSuccess ||
-      hipMalloc(&d_n, 16) != hipSuccess) {
+  if (d_a.alloc(cnt) < 0 || d_b.alloc(cnt) < 0 || d_n.alloc(2) < 0) {
     rc = -ENOMEM; set_error("kc_fpset_check_fps: out of device memory");
   }
   if (!rc) {
@@ -762,21 +705,17 @@ int kc_fpset_check_fps(kc_fpset* s, uint64_t* min_gap_out, double* prob_out) {
     if (n > cnt) { rc = -EIO; set_error("kc_fpset_check_fps: count mismatch"); }
   }
   if (!rc && n > 1) {
-    if (hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_a, d_b, (int)n, 0, 64, st) != hipSuccess) {
+    if (hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_a.p, d_b.p, (int)n, 0, 64, st) != hipSuccess) {
       rc = -EIO; set_error("kc_fpset_check_fps: sort");
     }
-    if (!rc && hipMalloc(&tmp, tmp_bytes) != hipSuccess) { rc = -ENOMEM; set_error("kc_fpset_check_fps: temp"); }
+    if (!rc && tmp.alloc(tmp_bytes) < 0) { rc = -ENOMEM; set_error("kc_fpset_check_fps: temp"); }
     if (!rc) {
-      (void)hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, d_a, d_b, (int)n, 0, 64, st);
+      (void)hipcub::DeviceRadixSort::SortKeys(tmp.p, tmp_bytes, d_a.p, d_b.p, (int)n, 0, 64, st);
       hipLaunchKernelGGL(k_min_gap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_b, n, d_n + 1);
       (void)hipMemcpyAsync(&gap, d_n + 1, 8, hipMemcpyDeviceToHost, st);
       if (hipStreamSynchronize(st) != hipSuccess) { rc = -EIO; set_error("kc_fpset_check_fps: HIP"); }
     }
   }
-  if (tmp) (void)hipFree(tmp);
-  if (d_a) (void)hipFree(d_a);
-  if (d_b) (void)hipFree(d_b);
-  if (d_n) (void)hipFree(d_n);
   if (rc) return rc;
   if (min_gap_out) *min_gap_out = gap;
   if (prob_out) *prob_out = (n > 1 && gap) ? 1.0 / (double)gap : 0.0;
@@ -800,10 +739,10 @@ int kc_fpset_stress(kc_fpset* s, uint64_t seed, uint64_t n, uint64_t batch, uint
   KC_HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   KC_TRY(s->fs.reserve(n, st));
-  hipEvent_t e0, e1, e2;
-  KC_HIP_TRY(hipEventCreate(&e0));
-  KC_HIP_TRY(hipEventCreate(&e1));
-  KC_HIP_TRY(hipEventCreate(&e2));
+  OwnedEvent e0, e1, e2;
+  KC_TRY(e0.create());
+  KC_TRY(e1.create());
+  KC_TRY(e2.create());
   KC_HIP_TRY(hipMemsetAsync(s->d_stats, 0, STAT_BYTES, st));
   KC_HIP_TRY(hipEventRecord(e0, st));
   for (uint64_t off = 0; off < n; off += batch) {
@@ -824,9 +763,6 @@ int kc_fpset_stress(kc_fpset* s, uint64_t seed, uint64_t n, uint64_t batch, uint
   float ms1 = 0, ms2 = 0;
   KC_HIP_TRY(hipEventElapsedTime(&ms1, e0, e1));
   KC_HIP_TRY(hipEventElapsedTime(&ms2, e1, e2));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipEventDestroy(e2);
   s->fs.count += stats[0];
   if (insert_seconds) *insert_seconds = ms1 * 1e-3;
   if (lookup_seconds) *lookup_seconds = ms2 * 1e-3;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "fpset_dev.h"
+#include "owned.h"
 
 namespace kc {
 
@@ -16,16 +17,18 @@ inline unsigned table_grid(uint64_t n) {
   return (unsigned)(g < 65536 ? (g ? g : 1) : 65536);
 }
 
+// (The three owners below free their tables in their destructors: the holder
+// makes their device current first, as for every owned buffer.)
 struct DevFpset {
-  unsigned long long* slots = nullptr;  // nbuckets * 8 u64
+  DeviceArray<unsigned long long> slots;   // nbuckets * 8 u64
   uint64_t nbuckets = 0;
-  uint64_t count = 0;                   // host-tracked number of stored fps
-  unsigned long long* d_fail = nullptr; // rehash failure counter
+  uint64_t count = 0;                      // host-tracked number of stored fps
+  DeviceArray<unsigned long long> d_fail;  // rehash failure counter
 
   uint64_t capacity() const { return nbuckets * 8; }
-  // allocate for >= min_slots slots (whole buckets), zeroed
+  // allocate for >= min_slots slots (whole buckets), zeroed, in place of
+  // what it held
   int init(uint64_t min_slots, hipStream_t st);
-  void release();
   // grow (rehash into 2x..) so that count + extra <= 75% of capacity
   int reserve(uint64_t extra, hipStream_t st);
 };
@@ -33,19 +36,22 @@ struct DevFpset {
 // Host owner of the engine's ClaimSet (fpset_dev.h): nslots 16-B entries,
 // or (compact, the first-claim mode) nslots u64 fp words at the same address.
 struct DevClaimSet {
-  ClaimEntry* t = nullptr;
+  // t.cap counts 16-B ClaimEntry units in both modes: nslots of them, or
+  // nslots / 2 under the compact table's nslots 8-B words (units(): rounded
+  // up, should nslots be odd)
+  DeviceArray<ClaimEntry> t;
   uint64_t nslots = 0;
   uint64_t count = 0;                   // host-tracked number of stored fps
-  unsigned long long* d_fail = nullptr;
+  DeviceArray<unsigned long long> d_fail;
   bool compact = false;                 // set before init(); fixed for the owner's life
 
   uint64_t capacity() const { return nslots; }
   uint64_t slot_bytes() const { return compact ? 8 : sizeof(ClaimEntry); }
-  unsigned long long* words() const { return reinterpret_cast<unsigned long long*>(t); }
+  uint64_t units(uint64_t slots) const { return (slots * slot_bytes() + sizeof(ClaimEntry) - 1) / sizeof(ClaimEntry); }
+  unsigned long long* words() const { return reinterpret_cast<unsigned long long*>(t.p); }
   uint32_t word_shift() const { return compact ? 0u : 1u; }   // slot i's fp word: words()[i << word_shift()]
   int init(uint64_t min_slots, hipStream_t st);
   int clear(hipStream_t st);
-  void release();
   // grow (rehash) so that count + extra <= 1/2 of capacity
   int reserve(uint64_t extra, hipStream_t st);
 };
@@ -56,10 +62,8 @@ void launch_claimset_insert_list(const uint64_t* d_fps, uint64_t n, const DevCla
 
 // Batch table used to dedup a batch by minimum order key.
 struct DevBatchTable {
-  BatchEntry* t = nullptr;
-  uint64_t cap = 0;  // allocated entries (power of two)
+  DeviceArray<BatchEntry> t;   // t.cap: allocated entries (power of two)
   int ensure(uint64_t entries, hipStream_t st);  // grow allocation if needed
-  void release();
 };
 
 // the rehash passes of reserve(): every entry of `old` into the zeroed `nw`;

@@ -659,15 +659,7 @@ class LiveBase {
 template <class M>
 class LiveT : public LiveBase {
  public:
-  ~LiveT() override {
-    void* dev[] = {a_.states, a_.parent, a_.level, a_.row, a_.edges, a_.table, a_.alive, a_.terminal,
-                   a_.stamp, a_.path, a_.ctr, d_trace_, a_.eproc, a_.enabled, a_.color, a_.comp, a_.sccw,
-                   a_.fair, a_.bpar};
-    for (void* p : dev)
-      if (p) (void)hipFree(p);
-    if (h_ctr_) (void)hipHostFree(h_ctr_);
-    if (st_) (void)hipStreamDestroy(st_);
-  }
+  ~LiveT() override { (void)hipSetDevice(cfg.device); }   // (the members free themselves on it)
   int tuple_words() const override { return M::TUPLE_WORDS; }
 
   int setup() override {
@@ -688,32 +680,37 @@ class LiveT : public LiveBase {
     a_.flags = flags_of(cfg);
     a_.prop = live.property;
     KC_HIP_TRY(hipSetDevice(cfg.device));
-    KC_HIP_TRY(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-    KC_HIP_TRY(hipMalloc(&a_.states, cap * M::W * sizeof(uint64_t)));
-    KC_HIP_TRY(hipMalloc(&a_.parent, cap * sizeof(uint32_t)));
-    KC_HIP_TRY(hipMalloc(&a_.level, cap * sizeof(uint32_t)));
-    KC_HIP_TRY(hipMalloc(&a_.row, cap * sizeof(uint2)));
-    KC_HIP_TRY(hipMalloc(&a_.edges, a_.max_edges * sizeof(uint32_t)));
-    KC_HIP_TRY(hipMalloc(&a_.table, a_.nslots * sizeof(LiveSlot)));
-    KC_HIP_TRY(hipMalloc(&a_.alive, cap));
-    KC_HIP_TRY(hipMalloc(&a_.terminal, cap));
-    KC_HIP_TRY(hipMalloc(&a_.stamp, cap * sizeof(uint32_t)));
+    KC_TRY(st_.create(hipStreamNonBlocking));
+    // an owner of n elements, and the kernels' plain struct reads its pointer
+    auto own = [](auto& arr, auto*& p, uint64_t n) {
+      KC_TRY(arr.alloc(n));
+      p = arr;
+      return 0;
+    };
+    KC_TRY(own(states_, a_.states, cap * M::W));
+    KC_TRY(own(parent_, a_.parent, cap));
+    KC_TRY(own(level_, a_.level, cap));
+    KC_TRY(own(row_, a_.row, cap));
+    KC_TRY(own(edges_, a_.edges, a_.max_edges));
+    KC_TRY(own(table_, a_.table, a_.nslots));
+    KC_TRY(own(alive_, a_.alive, cap));
+    KC_TRY(own(terminal_, a_.terminal, cap));
+    KC_TRY(own(stamp_, a_.stamp, cap));
     // per-process fairness: the lasso is the prefix and at most P + 2 legs, each shorter than the graph
     a_.path_cap = live.fairness == LF_Process ? cap * (uint64_t)(M::P + 3) : cap;
     a_.pmask = (1u << M::P) - 1u;
-    KC_HIP_TRY(hipMalloc(&a_.path, a_.path_cap * sizeof(uint32_t)));
+    KC_TRY(own(path_, a_.path, a_.path_cap));
     if (live.fairness == LF_Process) {
-      KC_HIP_TRY(hipMalloc(&a_.eproc, a_.max_edges));
-      KC_HIP_TRY(hipMalloc(&a_.enabled, cap));
-      KC_HIP_TRY(hipMalloc(&a_.color, cap * sizeof(uint32_t)));
-      KC_HIP_TRY(hipMalloc(&a_.comp, cap * sizeof(uint32_t)));
-      KC_HIP_TRY(hipMalloc(&a_.sccw, cap * sizeof(uint2)));
-      KC_HIP_TRY(hipMalloc(&a_.fair, cap));
-      KC_HIP_TRY(hipMalloc(&a_.bpar, cap * sizeof(uint32_t)));
+      KC_TRY(own(eproc_, a_.eproc, a_.max_edges));
+      KC_TRY(own(enabled_, a_.enabled, cap));
+      KC_TRY(own(color_, a_.color, cap));
+      KC_TRY(own(comp_, a_.comp, cap));
+      KC_TRY(own(sccw_, a_.sccw, cap));
+      KC_TRY(own(fair_, a_.fair, cap));
+      KC_TRY(own(bpar_, a_.bpar, cap));
     }
-    KC_HIP_TRY(hipMalloc(&a_.ctr, sizeof(LiveCounters)));
-    KC_HIP_TRY(hipHostMalloc(&h_ctr_, sizeof(LiveCounters)));
-    return 0;
+    KC_TRY(own(ctr_, a_.ctr, 1));
+    return h_ctr_.alloc(1);
   }
 
   int run(kc_live_result* res) override {
@@ -826,13 +823,7 @@ class LiveT : public LiveBase {
           return -EIO;
         }
       }
-      if ((uint64_t)len > trace_cap_) {
-        if (d_trace_) KC_HIP_TRY(hipFree(d_trace_));
-        d_trace_ = nullptr;
-        trace_cap_ = 0;
-        KC_HIP_TRY(hipMalloc(&d_trace_, (size_t)len * M::W * sizeof(uint64_t)));
-        trace_cap_ = len;
-      }
+      if ((uint64_t)len * M::W > d_trace_.cap) KC_TRY(d_trace_.renew((uint64_t)len * M::W));
       hipLaunchKernelGGL(k_live_gather, dim3(live_grid(len)), dim3(LIVE_BLOCK), 0, st_, a_.states, a_.path, len,
                          (int)M::W, d_trace_);
       KC_HIP_TRY(hipGetLastError());
@@ -1045,11 +1036,15 @@ class LiveT : public LiveBase {
     return 0;
   }
 
-  hipStream_t st_ = nullptr;
-  LiveArgs a_{};
-  LiveCounters* h_ctr_ = nullptr;
-  uint64_t* d_trace_ = nullptr;
-  uint64_t trace_cap_ = 0;
+  OwnedStream st_;   // (first: destroyed after every buffer below)
+  LiveArgs a_{};     // the kernels' view of the buffers below
+  DeviceArray<uint64_t> states_, d_trace_;
+  DeviceArray<uint32_t> parent_, level_, edges_, stamp_, path_, color_, comp_, bpar_;
+  DeviceArray<uint2> row_, sccw_;
+  DeviceArray<LiveSlot> table_;
+  DeviceArray<uint8_t> alive_, terminal_, eproc_, enabled_, fair_;
+  DeviceArray<LiveCounters> ctr_;
+  PinnedArray<LiveCounters> h_ctr_;
   std::vector<uint64_t> trace_;   // the counterexample's packed states
   uint64_t n_ = 0, ne_ = 0;
   bool ran_ = false;

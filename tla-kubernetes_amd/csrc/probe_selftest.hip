@@ -161,12 +161,8 @@ __global__ void __launch_bounds__(256) k_probe_lds(int sequential, const unsigne
 }
 
 struct ProbeBufs {
-  unsigned long long *w = nullptr, *old = nullptr, *res = nullptr, *fail = nullptr;
-  uint64_t *fps = nullptr, *keys = nullptr;
-  ~ProbeBufs() {
-    for (void* p : {(void*)w, (void*)old, (void*)res, (void*)fail, (void*)fps, (void*)keys})
-      if (p) (void)hipFree(p);
-  }
+  DeviceArray<unsigned long long> w, old, res, fail;
+  DeviceArray<uint64_t> fps, keys;
 };
 
 static int probe_run(int kind, uint64_t nslots, const uint64_t* fps, const uint64_t* keys, uint64_t n, uint32_t level,
@@ -180,19 +176,19 @@ static int probe_run(int kind, uint64_t nslots, const uint64_t* fps, const uint6
   const uint64_t nkeys = kind == PK_PAIR_STALE ? 2 * n : n;
   ProbeBufs b;
   hipStream_t st = nullptr;
-  KC_HIP_TRY(hipMalloc(&b.w, nslots * wps * 8));
+  KC_TRY(b.w.alloc(nslots * wps));
   if (table_in && !rehash) KC_HIP_TRY(hipMemcpy(b.w, table_in, nslots * wps * 8, hipMemcpyHostToDevice));
   else KC_HIP_TRY(hipMemset(b.w, 0, nslots * wps * 8));
-  KC_HIP_TRY(hipMalloc(&b.res, (nres ? nres : 1) * 8));
+  KC_TRY(b.res.alloc(nres ? nres : 1));
   KC_HIP_TRY(hipMemset(b.res, 0, (nres ? nres : 1) * 8));
   if (rehash) {
     // table_in: the old table of n slots; the new one has nslots
-    KC_HIP_TRY(hipMalloc(&b.old, n * wps * 8));
+    KC_TRY(b.old.alloc(n * wps));
     KC_HIP_TRY(hipMemcpy(b.old, table_in, n * wps * 8, hipMemcpyHostToDevice));
-    KC_HIP_TRY(hipMalloc(&b.fail, 8));
+    KC_TRY(b.fail.alloc(1));
     KC_HIP_TRY(hipMemset(b.fail, 0, 8));
     if (kind == PK_REHASH_CLAIMSET)
-      launch_claimset_rehash(reinterpret_cast<const ClaimEntry*>(b.old), n, reinterpret_cast<ClaimEntry*>(b.w), nslots,
+      launch_claimset_rehash(reinterpret_cast<const ClaimEntry*>(b.old.p), n, reinterpret_cast<ClaimEntry*>(b.w.p), nslots,
                              b.fail, st);
     else if (kind == PK_REHASH_FPSLOTS)
       launch_fpslots_rehash(b.old, n, b.w, nslots, b.fail, st);
@@ -201,16 +197,16 @@ static int probe_run(int kind, uint64_t nslots, const uint64_t* fps, const uint6
     KC_HIP_TRY(hipGetLastError());
     KC_HIP_TRY(hipMemcpy(b.res, b.fail, 8, hipMemcpyDeviceToDevice));
   } else if (n) {
-    KC_HIP_TRY(hipMalloc(&b.fps, n * 8));
+    KC_TRY(b.fps.alloc(n));
     KC_HIP_TRY(hipMemcpy(b.fps, fps, n * 8, hipMemcpyHostToDevice));
-    KC_HIP_TRY(hipMalloc(&b.keys, nkeys * 8));
+    KC_TRY(b.keys.alloc(nkeys));
     if (keys) KC_HIP_TRY(hipMemcpy(b.keys, keys, nkeys * 8, hipMemcpyHostToDevice));
     else KC_HIP_TRY(hipMemset(b.keys, 0, nkeys * 8));
     if (lds) {
       // (b.w doubles as the image in and out: the kernel reads it all before it writes)
-      KC_HIP_TRY(hipMalloc(&b.old, nslots * 16));
+      KC_TRY(b.old.alloc(nslots * 2));
       KC_HIP_TRY(hipMemcpy(b.old, b.w, nslots * 16, hipMemcpyDeviceToDevice));
-      const unsigned long long* img = table_in ? b.old : nullptr;
+      const unsigned long long* img = table_in ? b.old.p : nullptr;
       if (kind == PK_LDS)
         hipLaunchKernelGGL(k_probe_lds<CLAIM_LDS>, dim3(1), dim3(256), 0, st, mode == 0, img, b.fps, b.keys, n, b.res, b.w);
       else

@@ -1,5 +1,5 @@
 // selftest_util.h — host helpers shared by the test-only device harnesses
-// (spill_selftest.hip, emit_selftest.hip, coldset_selftest.hip): an owning device buffer, the
+// (spill_selftest.hip, emit_selftest.hip, coldset_selftest.hip): an untyped device buffer, the
 // upload of a host array, and the check that packed parents are states a
 // kernel may plan and apply.  Nothing of the product path includes this file.
 #pragma once
@@ -10,24 +10,19 @@
 
 #include "kc_common.h"
 #include "kubeapi_spec.h"
+#include "owned.h"
 
 namespace kc {
 namespace selftest {
 
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
+// bytes, read as whatever the kernel takes
+struct DevBuf : DeviceArray<uint8_t> {
   template <class T>
-  T* as() const { return static_cast<T*>(p); }
+  T* as() const { return reinterpret_cast<T*>(p); }
 };
 
 inline int upload(DevBuf& d, const void* src, uint64_t bytes) {
-  KC_HIP_TRY(hipMalloc(&d.p, bytes ? bytes : 8));
+  KC_TRY(d.alloc(bytes ? bytes : 8));
   if (bytes) KC_HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
   return 0;
 }

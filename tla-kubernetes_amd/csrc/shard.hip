@@ -943,7 +943,7 @@ class ShardT final : public ShardBase {
     // slots, half the table to clear; the narrow levels write no claim words)
     cs_.compact = first_;
   }
-  ~ShardT() override { release(); }
+  ~ShardT() override { (void)hipSetDevice(cfg_.device); }   // (the members free themselves on it)
 
   int setup() override {
     int ndev = 0;
@@ -970,7 +970,7 @@ class ShardT final : public ShardBase {
       return -EINVAL;
     }
     KC_HIP_TRY(hipSetDevice(cfg_.device));
-    KC_HIP_TRY(hipStreamCreateWithFlags(&st_.s, hipStreamNonBlocking));
+    KC_TRY(st_.create(hipStreamNonBlocking));
     KC_TRY(d_ctr_.alloc(1));
     KC_TRY(h_ctr_.alloc(1));
     KC_TRY(h_exp_.alloc(1));         // (kCtrHead bytes of it are used)
@@ -978,9 +978,8 @@ class ShardT final : public ShardBase {
     KC_TRY(d_ovf_cnt_.alloc(1));     // (zeroed by k_head_reset every level)
     KC_TRY(d_stage_cur_.alloc(1));   // (likewise)
     KC_TRY(h_owner_base_.alloc(16));
-    KC_HIP_TRY(hipEventCreate(&ev_[0]));
-    KC_HIP_TRY(hipEventCreate(&ev_[1]));
-    return 0;
+    KC_TRY(ev_[0].create());
+    return ev_[1].create();
   }
 
   // k_claim time (HIP events, cfg.timing != 0), launches and parents since
@@ -994,10 +993,7 @@ class ShardT final : public ShardBase {
   }
 
   int set_stream(hipStream_t st) override {
-    if (st_.own && st_.s) KC_HIP_TRY(hipStreamDestroy(st_.s));
-    st_.s = st;
-    st_.own = false;
-    return 0;
+    return st_.borrow(st);
   }
 
   int init(uint64_t* n_local) override {
@@ -1440,7 +1436,7 @@ class ShardT final : public ShardBase {
     }
     // else stream-ordered with the caller (set_stream, or the native level
     // loop, which synchronises before it moves the records itself)
-    if (st_.own && !async_pack_) KC_HIP_TRY(hipStreamSynchronize(st_));
+    if (st_.owned() && !async_pack_) KC_HIP_TRY(hipStreamSynchronize(st_));
     return 0;
   }
 
@@ -2086,15 +2082,6 @@ class ShardT final : public ShardBase {
   }
 
  private:
-  // What is not a buffer.  The buffers free themselves after this, with the
-  // device still current; the stream (st_, declared before them) goes last.
-  void release() {
-    (void)hipSetDevice(cfg_.device);
-    cs_.release();
-    for (auto& e : ev_)
-      if (e) (void)hipEventDestroy(e);
-  }
-
   kc_model_config cfg_;
   int rank_, world_;
   Flags flags_{};
@@ -2175,7 +2162,7 @@ class ShardT final : public ShardBase {
   bool dev_empty_ = false, dev_zero_ = false;
   int level_ = 0;
   std::vector<uint64_t> level_base_;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  OwnedEvent ev_[2];
   bool async_pack_ = false;
   // device-driven narrow levels
   DeviceArray<SNCtl> d_snc_;

@@ -146,16 +146,7 @@ class SimBase {
 template <class M>
 class SimT : public SimBase {
  public:
-  ~SimT() override {
-    if (d_state_) (void)hipFree(d_state_);
-    if (d_status_) (void)hipFree(d_status_);
-    if (d_ctr_) (void)hipFree(d_ctr_);
-    if (h_ctr_) (void)hipHostFree(h_ctr_);
-    fs_.release();
-    if (ev0_) (void)hipEventDestroy(ev0_);
-    if (ev1_) (void)hipEventDestroy(ev1_);
-    if (st_) (void)hipStreamDestroy(st_);
-  }
+  ~SimT() override { (void)hipSetDevice(cfg.device); }   // (the members free themselves on it)
   int tuple_words() const override { return M::TUPLE_WORDS; }
 
   int setup() override {
@@ -169,14 +160,13 @@ class SimT : public SimBase {
       return -EINVAL;
     }
     KC_HIP_TRY(hipSetDevice(cfg.device));
-    KC_HIP_TRY(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-    KC_HIP_TRY(hipEventCreate(&ev0_));
-    KC_HIP_TRY(hipEventCreate(&ev1_));
-    KC_HIP_TRY(hipMalloc(&d_state_, sim.num_walks * M::W_RAW * sizeof(uint64_t)));
-    KC_HIP_TRY(hipMalloc(&d_status_, sim.num_walks * sizeof(uint32_t)));
-    KC_HIP_TRY(hipMalloc(&d_ctr_, sizeof(SimCounters)));
-    KC_HIP_TRY(hipHostMalloc(&h_ctr_, sizeof(SimCounters)));
-    return 0;
+    KC_TRY(st_.create(hipStreamNonBlocking));
+    KC_TRY(ev0_.create());
+    KC_TRY(ev1_.create());
+    KC_TRY(d_state_.alloc(sim.num_walks * M::W_RAW));
+    KC_TRY(d_status_.alloc(sim.num_walks));
+    KC_TRY(d_ctr_.alloc(1));
+    return h_ctr_.alloc(1);
   }
 
   int run(kc_sim_result* res) override {
@@ -367,14 +357,14 @@ class SimT : public SimBase {
     return 0;
   }
 
-  hipStream_t st_ = nullptr;
-  hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-  uint64_t* d_state_ = nullptr;
-  uint32_t* d_status_ = nullptr;
-  SimCounters* d_ctr_ = nullptr;
-  SimCounters* h_ctr_ = nullptr;
+  OwnedStream st_;   // (first: destroyed after every buffer below)
+  DeviceArray<uint64_t> d_state_;
+  DeviceArray<uint32_t> d_status_;
+  DeviceArray<SimCounters> d_ctr_;
+  PinnedArray<SimCounters> h_ctr_;
   DevFpset fs_;
   bool ran_ = false;
+  OwnedEvent ev0_, ev1_;
 };
 
 std::unique_ptr<SimBase> make_sim(const kc_model_config& cfg) {

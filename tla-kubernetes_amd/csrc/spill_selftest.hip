@@ -55,7 +55,7 @@ int run_claimset_keys(const uint64_t* a, uint64_t na, uint64_t cap, uint64_t* ou
   DevBuf t, o, c;
   KC_TRY(upload(t, a, na * 16));
   KC_TRY(upload(o, out, nout * 8));
-  KC_HIP_TRY(hipMalloc(&c.p, 8));
+  KC_TRY(c.alloc(8));
   KC_HIP_TRY(hipMemset(c.p, 0, 8));
   hipLaunchKernelGGL(k_claimset_keys, dim3(table_grid(na)), dim3(256), 0, nullptr, t.as<const ClaimEntry>(), na,
                      o.as<uint64_t>(), cap, c.as<unsigned long long>());
@@ -147,7 +147,7 @@ int run_spill_apply(const uint64_t* a, uint64_t na, const uint64_t* b, uint64_t 
   KC_TRY(upload(df, fd.data(), m));
   KC_TRY(upload(dn, nm.data(), nc * 4));
   KC_TRY(upload(dt, tt.data(), tiles * 4));
-  KC_HIP_TRY(hipMalloc(&ctr.p, sizeof(Counters)));
+  KC_TRY(ctr.alloc(sizeof(Counters)));
   KC_HIP_TRY(hipMemset(ctr.p, 0, sizeof(Counters)));
   hipLaunchKernelGGL(k_spill_apply, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, dk.as<const uint64_t>(),
                      dl.as<const uint32_t>(), df.as<const uint8_t>(), m, dn.as<uint32_t>(), dt.as<uint32_t>(),
@@ -175,7 +175,7 @@ int run_tile_succ(const uint64_t* a, uint64_t na, uint64_t* res) {
   std::vector<uint32_t> ts(tiles);
   DevBuf cur, d;
   KC_TRY(upload(cur, a, na * M::W * 8));
-  KC_HIP_TRY(hipMalloc(&d.p, tiles * 4));
+  KC_TRY(d.alloc(tiles * 4));
   KC_HIP_TRY(hipMemset(d.p, 0xff, tiles * 4));
   hipLaunchKernelGGL(k_tile_succ<M>, dim3((unsigned)tiles), dim3(256), 0, nullptr, cur.as<const typename M::State>(),
                      na, test_flags(), d.as<uint32_t>());

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/kubecheck.h"
+#include "owned.h"
 
 namespace kc {
 
@@ -72,13 +73,13 @@ class SegQueue {
   struct Seg {
     uint64_t cap = 0, head = 0, tail = 0;   // states
     int tier = HBM;
-    uint64_t* dev = nullptr;
-    uint64_t* host = nullptr;
+    DeviceArray<uint64_t> dev;    // (a move-only owner; its file is the queue's to unlink)
+    PinnedArray<uint64_t> host;
     std::string path;
   };
   uint64_t bytes(uint64_t states) const { return states * (uint64_t)cfg_.words * 8; }
-  int dev_alloc(uint64_t cap, uint64_t** p, hipStream_t st, int64_t keep_hi);
-  void dev_release(uint64_t* p, uint64_t cap);
+  int dev_alloc(uint64_t cap, DeviceArray<uint64_t>& out, hipStream_t st, int64_t keep_hi);
+  void dev_release(DeviceArray<uint64_t>&& b, uint64_t cap);
   int spill_one(hipStream_t st, int64_t keep_hi, bool* done);
   int spill(Seg& s, hipStream_t st);
   int load(size_t idx, hipStream_t st);
@@ -88,14 +89,13 @@ class SegQueue {
 
   Config cfg_;
   std::deque<Seg> segs_;
-  std::vector<uint64_t*> pool_;            // free standard-size HBM buffers
+  std::vector<DeviceArray<uint64_t>> pool_;   // free standard-size HBM buffers
   uint64_t size_ = 0;
   uint64_t reserved_ = 0;                  // states reserved in the tail
   int64_t front_pin_ = -1;                 // segments 0..front_pin_ have handed out front runs
   uint64_t hbm_used_ = 0, host_used_ = 0, disk_used_ = 0, peak_hbm_ = 0;
   uint64_t spilled_host_ = 0, spilled_disk_ = 0, reloaded_ = 0;
-  uint64_t* stage_ = nullptr;              // pinned staging for the disk tier
-  uint64_t stage_cap_ = 0;                 // bytes
+  PinnedArray<uint8_t> stage_;             // staging for the disk tier
   uint64_t file_seq_ = 0;
   uint64_t id_ = 0;
 };

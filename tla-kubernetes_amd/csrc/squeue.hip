@@ -26,11 +26,8 @@ std::atomic<uint64_t> g_queue_ids{0};
 SegQueue::~SegQueue() {
   (void)hipSetDevice(cfg_.device);
   (void)hipDeviceSynchronize();
-  for (auto& s : segs_) (void)free_seg(s);
-  segs_.clear();
-  for (auto* p : pool_) (void)hipFree(p);
-  pool_.clear();
-  if (stage_) (void)hipHostFree(stage_);
+  for (const auto& s : segs_)     // (the buffers free themselves; the files are not theirs)
+    if (!s.path.empty()) unlink(s.path.c_str());
 }
 
 int SegQueue::init(const Config& c) {
@@ -45,37 +42,30 @@ int SegQueue::init(const Config& c) {
 }
 
 int SegQueue::staging(uint64_t b) {
-  if (b <= stage_cap_) return 0;
-  if (stage_) (void)hipHostFree(stage_);
-  stage_ = nullptr;
-  stage_cap_ = 0;
-  KC_HIP_TRY(hipHostMalloc(&stage_, b));
-  stage_cap_ = b;
-  return 0;
+  return b <= stage_.cap ? 0 : stage_.renew(b);
 }
 
-void SegQueue::dev_release(uint64_t* p, uint64_t cap) {
-  if (!p) return;
+void SegQueue::dev_release(DeviceArray<uint64_t>&& b, uint64_t cap) {
+  if (!b) return;
   if (cap == cfg_.seg_states && (cfg_.hbm_bytes == 0 || hbm_used_ <= cfg_.hbm_bytes)) {
-    pool_.push_back(p);            // stream-ordered reuse: still counted in hbm_used_
+    pool_.push_back(std::move(b));   // stream-ordered reuse: still counted in hbm_used_
     return;
   }
-  (void)hipFree(p);
+  b.reset();
   hbm_used_ -= bytes(cap);
 }
 
 // One HBM buffer of `cap` states.  Over budget: free pooled buffers, then
 // spill segments (never the back, never index <= keep_hi) until it fits or
 // nothing is left to spill (the segments being read and written always stay).
-int SegQueue::dev_alloc(uint64_t cap, uint64_t** p, hipStream_t st, int64_t keep_hi) {
+int SegQueue::dev_alloc(uint64_t cap, DeviceArray<uint64_t>& out, hipStream_t st, int64_t keep_hi) {
   if (cap == cfg_.seg_states && !pool_.empty()) {
-    *p = pool_.back();
+    out = std::move(pool_.back());
     pool_.pop_back();
     return 0;
   }
   while (cfg_.hbm_bytes && hbm_used_ + bytes(cap) > cfg_.hbm_bytes) {
     if (!pool_.empty()) {
-      (void)hipFree(pool_.back());
       pool_.pop_back();
       hbm_used_ -= bytes(cfg_.seg_states);
       continue;
@@ -84,7 +74,7 @@ int SegQueue::dev_alloc(uint64_t cap, uint64_t** p, hipStream_t st, int64_t keep
     KC_TRY(spill_one(st, keep_hi, &done));
     if (!done) break;
   }
-  KC_HIP_TRY(hipMalloc(p, bytes(cap)));
+  KC_TRY(out.renew(cap * (uint64_t)cfg_.words));
   hbm_used_ += bytes(cap);
   peak_hbm_ = std::max(peak_hbm_, hbm_used_);
   return 0;
@@ -109,11 +99,11 @@ int SegQueue::spill(Seg& s, hipStream_t st) {
   const uint64_t live = s.tail - s.head, b = bytes(live);
   const uint64_t* src = s.dev + s.head * cfg_.words;
   if (cfg_.host_bytes == 0 || host_used_ + b <= cfg_.host_bytes) {
-    uint64_t* h = nullptr;
-    KC_HIP_TRY(hipHostMalloc(&h, b ? b : 8));
+    PinnedArray<uint64_t> h;
+    KC_TRY(h.alloc(b ? b / 8 : 1));
     if (b) KC_HIP_TRY(hipMemcpyAsync(h, src, b, hipMemcpyDeviceToHost, st));
     KC_HIP_TRY(hipStreamSynchronize(st));
-    s.host = h;
+    s.host = std::move(h);
     s.tier = HOST;
     host_used_ += b;
     spilled_host_ += b;
@@ -145,8 +135,7 @@ int SegQueue::spill(Seg& s, hipStream_t st) {
               (unsigned long long)cfg_.hbm_bytes, (unsigned long long)cfg_.host_bytes);
     return -ENOMEM;
   }
-  dev_release(s.dev, s.cap);
-  s.dev = nullptr;
+  dev_release(std::move(s.dev), s.cap);
   s.head = 0;
   s.tail = live;
   return 0;
@@ -156,15 +145,14 @@ int SegQueue::spill(Seg& s, hipStream_t st) {
 int SegQueue::load(size_t idx, hipStream_t st) {
   Seg& s = segs_[idx];
   if (s.tier == HBM) return 0;
-  uint64_t* p = nullptr;
-  KC_TRY(dev_alloc(s.cap, &p, st, std::max<int64_t>(front_pin_, (int64_t)idx)));
+  DeviceArray<uint64_t> p;
+  KC_TRY(dev_alloc(s.cap, p, st, std::max<int64_t>(front_pin_, (int64_t)idx)));
   Seg& t = segs_[idx];                               // (deque references survive; re-read anyway)
   const uint64_t b = bytes(t.tail);
   if (t.tier == HOST) {
     if (b) KC_HIP_TRY(hipMemcpyAsync(p, t.host, b, hipMemcpyHostToDevice, st));
     KC_HIP_TRY(hipStreamSynchronize(st));
-    (void)hipHostFree(t.host);
-    t.host = nullptr;
+    t.host.reset();
     host_used_ -= b;
   } else {
     KC_TRY(staging(b ? b : 8));
@@ -186,16 +174,15 @@ int SegQueue::load(size_t idx, hipStream_t st) {
     disk_used_ -= b;
   }
   reloaded_ += b;
-  t.dev = p;
+  t.dev = std::move(p);
   t.tier = HBM;
   return 0;
 }
 
 int SegQueue::free_seg(Seg& s) {
   if (s.tier == HBM) {
-    dev_release(s.dev, s.cap);
+    dev_release(std::move(s.dev), s.cap);
   } else if (s.tier == HOST) {
-    if (s.host) (void)hipHostFree(s.host);
     host_used_ -= bytes(s.tail);
   } else {
     if (!s.path.empty()) unlink(s.path.c_str());
@@ -215,13 +202,13 @@ int SegQueue::new_tail(uint64_t n, hipStream_t st) {
   // to make room for it
   segs_.push_back(Seg{});
   segs_.back().cap = std::max(cfg_.seg_states, n);
-  uint64_t* p = nullptr;
-  const int rc = dev_alloc(segs_.back().cap, &p, st, front_pin_);
+  DeviceArray<uint64_t> p;     // (dev_alloc may spill segments: not a reference into segs_)
+  const int rc = dev_alloc(segs_.back().cap, p, st, front_pin_);
   if (rc < 0) {
     segs_.pop_back();
     return rc;
   }
-  segs_.back().dev = p;
+  segs_.back().dev = std::move(p);
   return 0;
 }
 
@@ -429,8 +416,8 @@ void SegQueue::stats(kc_squeue_stats* o) const {
 using namespace kc;
 
 struct kc_squeue {
-  SegQueue q;
-  hipStream_t st = nullptr;       // the queue's own stream (blocking: ordered with the null stream)
+  OwnedStream st;                 // the queue's own stream (blocking: ordered with the null stream);
+  SegQueue q;                     // before the queue: destroyed after its buffers
   int device = 0;
   uint64_t max_states = 0;        // kc_squeue_create's capacity: a hard bound (0 = none)
   std::mutex mu;
@@ -474,7 +461,7 @@ int kc_squeue_create2(const kc_squeue_config* c, kc_squeue** out) {
   auto* q = new kc_squeue();
   q->device = c->device;
   int rc = q->q.init(qc);
-  if (rc == 0 && hipStreamCreate(&q->st) != hipSuccess) {
+  if (rc == 0 && q->st.create(hipStreamDefault) < 0) {
     set_error("kc_squeue_create: stream creation failed");
     rc = -EIO;
   }
@@ -508,7 +495,6 @@ void kc_squeue_destroy(kc_squeue* q) {
     (void)hipSetDevice(q->device);
     (void)q->q.clear(q->st);
   }
-  if (q->st) (void)hipStreamDestroy(q->st);
   delete q;
 }
 

@@ -51,7 +51,7 @@ int run_fps(const uint64_t* tuples, uint64_t n, uint64_t* fps) {
   if (n == 0) return 0;
   DevBuf in, out;
   KC_TRY(selftest::upload(in, packed.data(), packed.size() * 8));
-  KC_HIP_TRY(hipMalloc(&out.p, n * 8));
+  KC_TRY(out.alloc(n * 8));
   hipLaunchKernelGGL(k_sym_fps<M>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr,
                      in.as<const uint64_t>(), n, out.as<unsigned long long>());
   KC_HIP_TRY(hipGetLastError());
