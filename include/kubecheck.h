@@ -346,6 +346,18 @@ int kc_engine_trace_tuple(kc_engine *e, int i, uint64_t *out);
 int64_t kc_engine_level_tuples(kc_engine *e, int level, uint64_t *out, uint64_t cap_states);
 /* Ask run() to keep a host copy of level `level`'s packed states. */
 int kc_engine_capture_level(kc_engine *e, int level);
+/* Expression-level coverage (TLC's -coverage).  With
+ * coverage on, run() also sums kc_cover_count() base counters over every
+ * state it expands (levels 1..max_levels-1 of a bounded run): one counting
+ * kernel per level next to the engine's own, and one host sync per narrow
+ * level.  Off (the default) the engine allocates and launches what it always
+ * did.  -EINVAL for an engine under symmetry reduction (its states stand for
+ * orbits) and with seen_hbm_bytes, frontier_hbm_bytes or trace_host. */
+int kc_engine_set_coverage(kc_engine *e, int on);
+/* The summed counters of the last run, in kc_cover_name order; returns the
+ * number written (cap >= kc_cover_count()).  -EINVAL when coverage was off,
+ * and after a run that ended in an error (TLC prints no coverage then). */
+int kc_engine_coverage(kc_engine *e, uint64_t *out, int cap);
 /* Per-kernel device timings of the last run (ms; needs cfg.timing=1, or 2
  * for expand alone):
  * expand, resolve, scan, emit; and the number of launches of each. */
@@ -831,6 +843,13 @@ int kc_spec_successors(const kc_model_config *cfg, const uint64_t *tuple, int *a
                        uint64_t *succ_tuples_out, int cap, int *fail_action);
 /* TypeOK/OnlyOneVersion: -1 = both hold, 0 = TypeOK fails, 1 = OOV fails. */
 int kc_spec_check(const kc_model_config *cfg, const uint64_t *tuple);
+/* Coverage base counters (csrc/cover.h) summed over n canonical tuples, each
+ * taken as a state the BFS expands: the host definition of what
+ * kc_engine_coverage counts.  sums_out holds kc_cover_count() words. */
+int kc_spec_cover(const kc_model_config *cfg, const uint64_t *tuples, uint64_t n, uint64_t *sums_out);
+int kc_cover_count(void);
+/* Name of counter i, or NULL. */
+const char *kc_cover_name(int i);
 /* Fingerprint of the packed form of a canonical tuple. */
 int kc_spec_fingerprint(const kc_model_config *cfg, const uint64_t *tuple, uint64_t *fp_out);
 /* Self-check of the kernels' incremental fingerprint: the number of

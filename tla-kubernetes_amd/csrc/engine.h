@@ -36,6 +36,10 @@ class EngineBase {
   virtual int tuple_words() const = 0;
   virtual int check_fps(uint64_t* min_gap, double* prob) = 0;
   void set_capture(int level) { capture_level_ = level; }
+  // expression-level coverage (cover.h): count every expanded state's base
+  // counters from the next run on; the last run's sums
+  virtual int set_coverage(bool on) = 0;
+  virtual int coverage(uint64_t* out, int cap) const = 0;
   void set_timing(bool on) { timing_ = on ? 1 : 0; }
   void kernel_times(double* ms, uint64_t* launches) const {
     for (int k = 0; k < KK_COUNT; ++k) {
@@ -65,6 +69,10 @@ std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg);
 // non-trivial group (kubeapi_spec.h sym_effective); nullptr for other models
 std::unique_ptr<EngineBase> make_engine_sym(const kc_model_config& cfg, int eff);
 const char* action_name(int a);
+// k_cover (cover.hip) over n packed states of cfg's plain Model on `stream`
+// (a hipStream_t): their coverage base counters added into d_sums[KC_COVER_N]
+int cover_launch(const kc_model_config& cfg, const void* states, uint64_t n, unsigned long long* d_sums,
+                 void* stream);
 // TLA+-style rendering of a canonical tuple (spec_abi.cpp)
 std::string format_tuple(const uint64_t* tuple, int nc, int np, int ns, bool ghost = false);
 

@@ -14,6 +14,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <memory>
 #include <string>
@@ -22,6 +23,7 @@
 #include "../../include/kubecheck.h"
 #include "claim_launch.h"
 #include "coldset.h"
+#include "cover.h"
 #include "engine.h"
 #include "engine_kernels.h"
 #include "engine_narrow.h"
@@ -270,7 +272,67 @@ class EngineT final : public EngineBase {
       res->defer_fallback = 1;
       res->defer_redo_level = 1;
     }
+    cover_valid_ = cover_on_ && rc == 0 && res->err_kind == 0;
     return rc;
+  }
+
+  // ---- expression-level coverage (cover.h).  k_cover runs
+  // over each expanded level's parents where they are resident in cur_; a
+  // level's sums go to the host at the level's own sync and count once the
+  // level is closed (a level the deferred frontier redoes is dropped first).
+  int set_coverage(bool on) override {
+    if (on && !std::is_same<Model<M::NC, M::NP, M::NS>, M>::value) {   // (a SymModel)
+      set_error("kc_engine_set_coverage: not under symmetry reduction (the states explored stand for orbits)");
+      return -EINVAL;
+    }
+    if (on && (spill_ || queued_ || cfg_.trace_host || ablate_)) {
+      set_error("kc_engine_set_coverage: not with seen_hbm_bytes, frontier_hbm_bytes or trace_host");
+      return -EINVAL;
+    }
+    cover_on_ = on;
+    cover_valid_ = false;
+    return 0;
+  }
+  int coverage(uint64_t* out, int cap) const override {
+    if (!out || cap < KC_COVER_N) {
+      set_error("kc_engine_coverage: NULL or fewer than %d words", KC_COVER_N);
+      return -EINVAL;
+    }
+    if (!cover_valid_) {
+      set_error(cover_on_ ? "kc_engine_coverage: the last run ended in an error (or there was none)"
+                          : "kc_engine_coverage: coverage is off (kc_engine_set_coverage)");
+      return -EINVAL;
+    }
+    for (int k = 0; k < KC_COVER_N; ++k) out[k] = 0;
+    for (const auto& lv : cover_levels_)
+      for (int k = 0; k < KC_COVER_N; ++k) out[k] += lv.second[k];
+    return KC_COVER_N;
+  }
+  int cover_begin() {
+    cover_levels_.clear();
+    if (!cover_on_) return 0;
+    KC_TRY(d_cover_.alloc(KC_COVER_N));
+    KC_TRY(h_cover_.alloc(KC_COVER_N));
+    KC_HIP_TRY(hipMemsetAsync(d_cover_, 0, KC_COVER_N * 8, st_));
+    return 0;
+  }
+  // parents [start, start + cn) of the level in cur_
+  int cover_count(uint64_t start, uint64_t cn) {
+    return cover_launch(cfg_, cur_.p + start, cn, d_cover_.p, st_);
+  }
+  // the level's sums to the host and the device vector clear again (enqueued; valid after the next sync)
+  int cover_fetch() {
+    KC_HIP_TRY(hipMemcpyAsync(h_cover_, d_cover_, KC_COVER_N * 8, hipMemcpyDeviceToHost, st_));
+    KC_HIP_TRY(hipMemsetAsync(d_cover_, 0, KC_COVER_N * 8, st_));
+    return 0;
+  }
+  void cover_commit(int level) {
+    std::array<uint64_t, KC_COVER_N> v;
+    for (int k = 0; k < KC_COVER_N; ++k) v[k] = h_cover_[k];
+    cover_levels_.emplace_back(level, v);
+  }
+  void cover_drop_from(int level) {
+    while (!cover_levels_.empty() && cover_levels_.back().first >= level) cover_levels_.pop_back();
   }
 
   // Where the BFS stands at the top of a level.
@@ -300,6 +362,7 @@ class EngineT final : public EngineBase {
   int run_once(kc_result* res) {
     KC_HIP_TRY(hipSetDevice(cfg_.device));
     reset_run(res);
+    KC_TRY(cover_begin());
     LevelCursor c;
     std::vector<State> init;
     int rc = seed_init(res, c, init);
@@ -476,10 +539,22 @@ class EngineT final : public EngineBase {
     pc_valid_ = false;
     int stop = cfg_.max_levels;
     if (capture_level_ >= c.level + 1 && (stop == 0 || capture_level_ - 1 < stop)) stop = capture_level_ - 1;
+    // coverage: one level per run, counted from cur_ before the run expands it
+    if (cover_on_ && (stop == 0 || c.level + 1 < stop)) stop = c.level + 1;
     const int level0 = c.level;
     const uint64_t n0 = c.n;
     NarrowRun nr;
     KC_TRY(run_narrow(c, stop, nr));
+    if (cover_on_ && nr.counted) {
+      // (a run that took no level leaves it to the wide path, which counts it again)
+      KC_TRY(cover_fetch());
+      KC_HIP_TRY(hipStreamSynchronize(st_));
+      if (nr.levels > 1) {
+        set_error("kubecheck: coverage: the narrow kernel ran %d levels in one run", nr.levels);
+        return -EIO;
+      }
+      if (nr.levels == 1) cover_commit(level0);
+    }
     res->distinct += nr.new_total;
     for (int L = level0; L < c.level; ++L) {
       if (L >= KC_MAX_LEVELS) {
@@ -598,6 +673,8 @@ class EngineT final : public EngineBase {
       }
     });
     if (ablate_) KC_TRY(ablate_claims(start, cn, tiles, succ_level));
+    // coverage: the chunk's parents are in cur_ (a deferred level's k_claim has just rebuilt and stored them)
+    if (cover_on_) KC_TRY(cover_count(start, cn));
     // (a small chunk: the overflow list's pass B inside the tile scan's launch)
     const bool fuse = tscan_ && cn <= FUSE_OVF_SCAN_MAX && !first_claim_;
     if (!first_claim_)
@@ -683,6 +760,7 @@ class EngineT final : public EngineBase {
       KC_HIP_TRY(hipMemcpyAsync(h_ctr_, d_ctr_, kCtrHead, hipMemcpyDeviceToHost, st_));
       hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_.p);   // next level's head
     }
+    if (cover_on_) KC_TRY(cover_fetch());
     KC_HIP_TRY(hipStreamSynchronize(st_));
     collect_times();
     const Counters& h = *h_ctr_;
@@ -711,6 +789,7 @@ class EngineT final : public EngineBase {
       const int X = (h.defer_flags & DF_INVARIANT) ? c.level - 1 : c.level;
       const uint64_t dc_here = h.cand_total - c.cand_total;
       if (!redo_from(X, dc_here, res, c)) return kDeferRetry;
+      cover_drop_from(X);            // levels X.. run again and are counted then
       pc_valid_ = false;
       return 0;
     }
@@ -728,6 +807,7 @@ class EngineT final : public EngineBase {
       return kRunDone;
     }
     res->distinct += n_new;
+    if (cover_on_) cover_commit(c.level);
     if (cfg_.verbose)
       fprintf(stderr, "kubecheck: level %d width %llu -> %llu new, %llu distinct\n",
               c.level, (unsigned long long)c.n, (unsigned long long)n_new,
@@ -1113,6 +1193,7 @@ class EngineT final : public EngineBase {
   struct NarrowRun {
     uint64_t new_total = 0, peak = 0;
     int levels = 0, reason = 0;
+    bool counted = false;          // coverage: k_cover ran over the run's first level
   };
   int run_narrow(LevelCursor& c, int stop, NarrowRun& nr) {
     const uint64_t n = c.n, level_gidx = c.level_gidx, cand = c.cand;
@@ -1154,6 +1235,10 @@ class EngineT final : public EngineBase {
     // block, so the ones after the run has ended return at once
     State *a = cur_.p, *b = next_.p;
     uint32_t lev = 0;                            // level launches enqueued in this run
+    if (cover_on_) {
+      KC_TRY(cover_count(0, n));
+      nr.counted = true;
+    }
     // the run's first level is expanded on its own; every k_nfinish then
     // expands the states it emits for the level after it
     hipLaunchKernelGGL(k_nexpand<M>, dim3(NARROW_WG * NARROW_SUB), dim3(NARROW_THREADS), 0, st_, a, b, flags_,
@@ -1164,7 +1249,8 @@ class EngineT final : public EngineBase {
       // a level is its in-kernel chain, not the launches; removed,
       // profiles/r06g_model1_narrow_graph_ab.log)
       timed(KK_NARROW, [&] {
-        for (int k = 0; k < narrow_batch_; ++k, ++lev)
+        // (coverage: the run stops after its first level, which one k_nfinish closes)
+        for (int k = 0; k < (cover_on_ ? 1 : narrow_batch_); ++k, ++lev)
           hipLaunchKernelGGL(k_nfinish<M>, dim3(NARROW_FWG), dim3(NARROW_THREADS), 0, st_, a, b, flags_,
                              cfg_.check_deadlock, tf_.parent(), tf_.ord(), cfg_.keep_trace, lev, d_ns_.p, d_nsc_.p,
                              cs_.t, cs_.nslots, d_ctr_.p, d_ntrace_.p, cs_.word_shift());
@@ -1725,6 +1811,10 @@ class EngineT final : public EngineBase {
   DeviceArray<unsigned long long> d_ntrace_;
 
   Flags flags_{};
+  bool cover_on_ = false, cover_valid_ = false;
+  DeviceArray<unsigned long long> d_cover_;      // the current level's sums
+  PinnedArray<unsigned long long> h_cover_;
+  std::vector<std::pair<int, std::array<uint64_t, KC_COVER_N>>> cover_levels_;   // (level, its sums), closed levels
   ShardArgs claim_args_{};
   bool queued_ = false;
   std::unique_ptr<SegQueue> q_;
@@ -1901,6 +1991,16 @@ int kc_engine_capture_level(kc_engine* e, int level) {
   if (!e) { set_error("kc_engine_capture_level: NULL"); return -EINVAL; }
   e->impl->set_capture(level);
   return 0;
+}
+
+int kc_engine_set_coverage(kc_engine* e, int on) {
+  if (!e) { set_error("kc_engine_set_coverage: NULL"); return -EINVAL; }
+  return e->impl->set_coverage(on != 0);
+}
+
+int kc_engine_coverage(kc_engine* e, uint64_t* out, int cap) {
+  if (!e) { set_error("kc_engine_coverage: NULL"); return -EINVAL; }
+  return e->impl->coverage(out, cap);
 }
 
 int kc_engine_narrow_times(kc_engine* e, double* ms, uint64_t* launches, uint64_t* levels) {

@@ -163,6 +163,9 @@ class CheckResult:
     claim_mode: str = "minimum"    # the claims that ran: "minimum" (sequential-BFS / rank-major), "first", "tlc"
     trace: List[List[int]] = field(default_factory=list)
     trace_text: str = ""
+    # expression-level coverage (run(coverage=True)): base counter name -> its
+    # sum over the states expanded; None when off or after an error
+    coverage: Optional[Dict[str, int]] = None
 
     @property
     def distinct_per_sec(self) -> float:
@@ -170,6 +173,12 @@ class CheckResult:
 
 
 CLAIM_MODES = {0: "minimum", 1: "first", 2: "tlc"}
+
+
+def cover_names() -> List[str]:
+    """Names of the coverage base counters, in the order of the C-ABI's vector."""
+    lib = load()
+    return [lib.kc_cover_name(i).decode() for i in range(lib.kc_cover_count())]
 
 
 def _result(r: KcResult) -> CheckResult:
@@ -200,21 +209,38 @@ def _result(r: KcResult) -> CheckResult:
 class ModelChecker:
     """BFS safety checker (TLC's ModelChecker for this spec) on one GPU."""
 
-    def __init__(self, cfg: Optional[ModelConfig] = None, **kw):
+    def __init__(self, cfg: Optional[ModelConfig] = None, *, coverage: bool = False, **kw):
         self.cfg = cfg or ModelConfig(**kw)
         self._lib = load()
         self._h = C.c_void_p()
         self._c = self.cfg.to_c()
         check("kc_engine_create", self._lib.kc_engine_create(C.byref(self._c), C.byref(self._h)))
         self.tuple_words = self._lib.kc_spec_tuple_words(self.cfg.nc, self.cfg.np, self.cfg.ns)
+        self._coverage = False
+        if coverage:
+            self.set_coverage(True)
+
+    def set_coverage(self, on: bool) -> None:
+        """Count expression-level coverage (TLC's -coverage) in the runs that
+        follow.  Refused under symmetry reduction and with the spill options."""
+        check("kc_engine_set_coverage", self._lib.kc_engine_set_coverage(self._h, int(bool(on))))
+        self._coverage = bool(on)
 
     def capture_level(self, level: int) -> None:
         check("kc_engine_capture_level", self._lib.kc_engine_capture_level(self._h, level))
 
-    def run(self) -> CheckResult:
+    def run(self, coverage: Optional[bool] = None) -> CheckResult:
+        """coverage: True / False switches it for this and later runs; None keeps the setting."""
+        if coverage is not None and bool(coverage) != self._coverage:
+            self.set_coverage(coverage)
         r = KcResult()
         check("kc_engine_run", self._lib.kc_engine_run(self._h, C.byref(r)))
         res = _result(r)
+        if self._coverage and res.error is None:
+            n = self._lib.kc_cover_count()
+            out = (C.c_uint64 * n)()
+            check("kc_engine_coverage", self._lib.kc_engine_coverage(self._h, out, n))
+            res.coverage = {k: int(out[i]) for i, k in enumerate(cover_names())}
         if res.error is not None and res.trace_len:
             res.trace = [self.trace_tuple(i) for i in range(res.trace_len)]
             n = self._lib.kc_engine_trace_text(self._h, None, 0)
@@ -749,6 +775,16 @@ class Spec:
             return None, ACTIONS[fail.value]
         check("kc_spec_successors", n)
         return [(ACTIONS[acts[i]], out[i]) for i in range(n)], None
+
+    def cover(self, tuples) -> Dict[str, int]:
+        """Coverage base counters summed over canonical tuples (n x tuple_words),
+        each taken as a state the BFS expands: the host definition of
+        CheckResult.coverage."""
+        t = np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, self.tuple_words)
+        n = self._lib.kc_cover_count()
+        out = (C.c_uint64 * n)()
+        check("kc_spec_cover", self._lib.kc_spec_cover(C.byref(self._c), _u64(t), t.shape[0], out))
+        return {k: int(out[i]) for i, k in enumerate(cover_names())}
 
     def check_invariants(self, tup) -> Optional[str]:
         t = np.ascontiguousarray(tup, dtype=np.uint64)

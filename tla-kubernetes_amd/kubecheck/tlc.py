@@ -3,7 +3,7 @@
     python -m kubecheck.tlc [-config MC.cfg] [-deadlock] [-tool] [-nc N -np N -ns N]
                             [-variant V] [-workers N] [-fp K]
                             [-simulate [num=N]] [-depth D] [-seed S] [-continue]
-                            [-fairness next|process] [MC]
+                            [-fairness next|process] [-coverage [minutes]] [MC]
 
 Reads the same inputs as the reference's toolbox run: a TLC model config
 (KubeAPI.toolbox/Model_1/MC.cfg:1-16 — CONSTANT assignments, either direct
@@ -13,8 +13,8 @@ SPECIFICATION; INVARIANT) and prints TLC's `-tool` message stream
 reference run shows (MC.out: 2262, 2187, 2185, 2189/2190, 2193 with both
 collision estimates, 2201/2773/2772/2202 coverage with TLC's source spans,
 2200 progress, 2199, 2194, 2268 outdegree, 2186) plus violation reports.
-SANY's messages (2220/2219) and expression-level coverage (2221) are not
-produced (no TLA+ front end).  The model check itself
+SANY's messages (2220/2219) are not produced (no TLA+ front end).  The
+model check itself
 runs on the GPU (kubecheck.ModelChecker); -workers and -fp are accepted for
 command-line compatibility (the GPU replaces the worker pool; fingerprints
 are kubecheck's own 64-bit hash, not TLC's FP64 #K).
@@ -58,6 +58,21 @@ SymActors (both).  The 2187 banner then names the set, and the distinct
 counts are orbit counts.  SYMMETRY together with a PROPERTY list or with
 -simulate is an error (liveness under symmetry is unsound, as TLC warns; a
 random walk has no seen-set to reduce).  Without the keyword nothing changes.
+
+Expression-level coverage: with `-coverage` (TLC's flag; its optional
+argument, the minutes between periodic reports, is accepted and ignored: only
+the final block is printed) the engine also counts, on the GPU and over every
+state it expands, the base counters of DESIGN.md §4.9, and the coverage block
+carries TLC's per-expression lines between the per-action ones: 2221 (one
+evaluation count per sub-expression), 2775 (count:cost of a set constructor)
+and the 2774 headers of the invariants, in the order and with the spans of
+MC.out:47-1090 (the table COVERAGE_LINES).  For Model_1 every count equals the
+reference run's.  Five of the eight cost figures are not derived
+(COVERAGE_COST_UNKNOWN): those lines print their count alone.  For other
+process counts the lines are the same expressions with self sets of NC clients
+and NP controllers; TLC pins none of them.  After a run that ends in an error
+the block has the per-action lines only.  -coverage with -simulate, a PROPERTY
+list or SYMMETRY is an error.  Without the flag nothing changes.
 
 `-fairness process` checks the properties under weak
 fairness of every process (PlusCal's `fair process`; a .cfg cannot say this,
@@ -174,13 +189,20 @@ def model_from_cfg(cfg: dict) -> dict:
     return kw
 
 
-def check_from_cfg(cfg: dict, simulate: bool = False):
+def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False):
     """model_from_cfg for a cfg that may list temporal properties: (ModelConfig
     kwargs, the PROPERTY names in cfg order).  The names must be kubecheck's
-    PROPERTIES; simulation mode checks none."""
+    PROPERTIES; simulation mode checks none.  coverage: -coverage was given."""
     from ._lib import PROPERTIES
 
     props = list(cfg["properties"])
+    if coverage and simulate:
+        raise CfgError("-coverage with -simulate: expression-level coverage is counted by the BFS only")
+    if coverage and props:
+        raise CfgError("-coverage with a PROPERTY list: expression-level coverage is counted by the BFS only")
+    if coverage and cfg.get("symmetry"):
+        raise CfgError(f"-coverage with SYMMETRY {cfg['symmetry']}: the states explored stand for orbits, "
+                       "so the counts would be no evaluation counts")
     bad = [x for x in props if x not in PROPERTIES]
     if bad:
         raise CfgError(f"unknown temporal property(ies) {bad}; known: {PROPERTIES}")
@@ -214,6 +236,416 @@ ACTION_SPANS = {
     "C5": (645, 1, 645, 8), "PVCStart": (655, 1, 655, 14), "PVCListedPVCs": (665, 1, 665, 19),
     "PVCHavePVCs": (673, 1, 673, 17), "PVCDone": (690, 1, 690, 13), "APIStart": (698, 1, 698, 14),
 }
+
+
+# Expression-level coverage (TLC's -coverage): every message
+# of the reference run's coverage block (MC.out:47-1090) in its order, as
+#   (message code, nesting depth, span in KubeAPI.tla, formula[, cost formula]).
+# 2773 / 2772 / 2774 rows head Init, an action or an invariant and carry its
+# name in the formula's place.  A 2221 / 2775 formula is a fixed integer
+# combination of the run's summed base counters (csrc/cover.h, the names of
+# kubecheck.cover_names()), gen_<Action> (act_gen), init, and the sizes of the
+# self sets P = |ProcSet|, NC, NP, NS.  The rules behind them:
+#   * a guard conjunct counts its evaluations plus the pairs that go on to
+#     produce a successor: |self set| * states + enabled pairs;
+#   * \E and CHOOSE over apiState stop at the first match, a set comprehension
+#     visits every element, in the order Secret before PVC;
+#   * an argument bound to a primed expression is evaluated at every use
+#     (:722 requests'[c].obj: once per o1.n and once more per o1.k).
+# A 2775 cost is count + the sizes of the sets built where that explains the
+# recorded number; None where it does not (COVERAGE_COST_UNKNOWN).
+COVERAGE_LINES = (
+    (2773, 0, (455, 1, 455, 4), 'Init'),
+    (2221, 0, (456, 12, 456, 24), '1'),
+    (2221, 0, (457, 12, 457, 39), '1'),
+    (2221, 0, (458, 12, 458, 43), '1'),
+    (2221, 0, (460, 12, 460, 56), '1'),
+    (2221, 0, (461, 12, 461, 57), '1'),
+    (2221, 0, (463, 12, 463, 58), '1'),
+    (2221, 0, (465, 12, 465, 54), '1'),
+    (2221, 0, (466, 12, 466, 47), 'init'),
+    (2221, 0, (467, 12, 469, 77), 'init'),
+    (2772, 0, (471, 1, 471, 15), 'DoRequest'),
+    (2221, 0, (471, 23, 471, 44), 'P*states + pairs_DoRequest'),
+    (2221, 1, (471, 23, 471, 30), 'P*states'),
+    (2221, 0, (472, 26, 475, 53), 'pairs_DoRequest'),
+    (2221, 0, (476, 29, 476, 69), 'pairs_DoRequest'),
+    (2221, 0, (477, 29, 480, 53), 'gen_DoRequest - pairs_DoRequest'),
+    (2221, 0, (481, 23, 481, 59), 'gen_DoRequest'),
+    (2221, 0, (482, 23, 483, 59), 'gen_DoRequest'),
+    (2772, 0, (485, 1, 485, 13), 'DoReply'),
+    (2221, 0, (485, 21, 485, 40), 'P*states + en_DoReply'),
+    (2221, 1, (485, 21, 485, 28), 'P*states'),
+    (2221, 0, (486, 21, 486, 53), 'pairs_DoReply + en_DoReply'),
+    (2221, 1, (486, 21, 486, 41), 'pairs_DoReply'),
+    (2221, 0, (487, 27, 487, 30), 'en_DoReply'),
+    (2221, 0, (488, 27, 488, 44), 'en_DoReply'),
+    (2221, 0, (489, 24, 490, 80), 'en_DoReply'),
+    (2221, 0, (491, 21, 491, 68), 'gen_DoReply'),
+    (2221, 0, (492, 21, 492, 68), 'gen_DoReply'),
+    (2221, 0, (493, 21, 493, 71), 'gen_DoReply'),
+    (2221, 0, (494, 21, 494, 71), 'gen_DoReply'),
+    (2221, 0, (495, 21, 495, 81), 'gen_DoReply'),
+    (2772, 0, (499, 1, 499, 19), 'DoListRequest'),
+    (2221, 0, (499, 27, 499, 52), 'P*states + pairs_DoListRequest'),
+    (2221, 1, (499, 27, 499, 34), 'P*states'),
+    (2221, 0, (500, 30, 503, 65), 'pairs_DoListRequest'),
+    (2221, 0, (504, 33, 504, 73), 'pairs_DoListRequest'),
+    (2221, 0, (505, 33, 508, 65), 'gen_DoListRequest - pairs_DoListRequest'),
+    (2221, 0, (509, 27, 509, 67), 'gen_DoListRequest'),
+    (2221, 0, (510, 27, 511, 63), 'gen_DoListRequest'),
+    (2772, 0, (513, 1, 513, 17), 'DoListReply'),
+    (2221, 0, (513, 25, 513, 48), 'P*states + en_DoListReply'),
+    (2221, 1, (513, 25, 513, 32), 'P*states'),
+    (2221, 0, (514, 25, 514, 61), 'pairs_DoListReply + en_DoListReply'),
+    (2221, 1, (514, 25, 514, 49), 'pairs_DoListReply'),
+    (2221, 0, (515, 31, 515, 34), 'en_DoListReply'),
+    (2221, 0, (516, 31, 516, 52), 'en_DoListReply'),
+    (2221, 0, (517, 28, 519, 92), 'en_DoListReply'),
+    (2221, 0, (520, 25, 520, 72), 'gen_DoListReply'),
+    (2221, 0, (521, 25, 521, 78), 'gen_DoListReply'),
+    (2221, 0, (522, 25, 522, 75), 'gen_DoListReply'),
+    (2221, 0, (523, 25, 524, 55), 'gen_DoListReply'),
+    (2772, 0, (528, 1, 528, 12), 'CStart'),
+    (2221, 0, (528, 20, 528, 38), 'NC*states + pairs_CStart'),
+    (2221, 1, (528, 20, 528, 27), 'NC*states'),
+    (2221, 0, (529, 23, 529, 83), 'pairs_CStart'),
+    (2221, 0, (530, 26, 530, 29), 'pairs_CStart'),
+    (2221, 0, (531, 26, 531, 50), 'pairs_CStart'),
+    (2221, 0, (532, 23, 532, 44), 'gen_CStart'),
+    (2221, 0, (533, 28, 541, 42), 'B_CSTART_THEN'),
+    (2221, 0, (542, 31, 546, 82), 'B_CSTART_ELSE'),
+    (2221, 0, (547, 31, 547, 73), 'B_CSTART_ELSE'),
+    (2221, 0, (548, 31, 548, 53), 'B_CSTART_ELSE'),
+    (2221, 0, (549, 20, 549, 67), 'gen_CStart'),
+    (2772, 0, (551, 1, 551, 8), 'C1'),
+    (2221, 0, (551, 16, 551, 30), 'NC*states + pairs_C1'),
+    (2221, 1, (551, 16, 551, 23), 'NC*states'),
+    (2221, 0, (552, 19, 552, 46), 'gen_C1'),
+    (2221, 0, (553, 24, 553, 62), 'B_C1_START'),
+    (2221, 0, (554, 24, 554, 59), 'B_C1_C10'),
+    (2221, 0, (555, 16, 556, 52), 'gen_C1'),
+    (2772, 0, (558, 1, 558, 9), 'C10'),
+    (2221, 0, (558, 17, 558, 32), 'NC*states + pairs_C10'),
+    (2221, 1, (558, 17, 558, 24), 'NC*states'),
+    (2221, 0, (559, 17, 565, 68), 'gen_C10'),
+    (2221, 0, (566, 17, 566, 55), 'gen_C10'),
+    (2221, 0, (567, 17, 568, 47), 'gen_C10'),
+    (2772, 0, (570, 1, 570, 9), 'C11'),
+    (2221, 0, (570, 17, 570, 32), 'NC*states + pairs_C11'),
+    (2221, 1, (570, 17, 570, 24), 'NC*states'),
+    (2221, 0, (571, 20, 571, 47), 'gen_C11'),
+    (2221, 0, (572, 25, 572, 63), 'B_C11_START'),
+    (2221, 0, (573, 25, 573, 60), 'B_C11_c12'),
+    (2221, 0, (574, 17, 575, 53), 'gen_C11'),
+    (2772, 0, (577, 1, 577, 9), 'c12'),
+    (2221, 0, (577, 17, 577, 32), 'NC*states + pairs_c12'),
+    (2221, 1, (577, 17, 577, 24), 'NC*states'),
+    (2221, 0, (578, 17, 584, 68), 'gen_c12'),
+    (2221, 0, (585, 17, 585, 55), 'gen_c12'),
+    (2221, 0, (586, 17, 587, 47), 'gen_c12'),
+    (2772, 0, (589, 1, 589, 9), 'C13'),
+    (2221, 0, (589, 17, 589, 32), 'NC*states + pairs_C13'),
+    (2221, 1, (589, 17, 589, 24), 'NC*states'),
+    (2221, 0, (590, 20, 590, 83), 'gen_C13'),
+    (2221, 1, (590, 20, 590, 47), 'gen_C13'),
+    (2221, 1, (590, 52, 590, 83), 'c13_ok'),
+    (2221, 2, (444, 22, 446, 58), 'c13_ok'),
+    (2221, 3, (444, 25, 444, 37), 'c13_ok'),
+    (2221, 3, (445, 25, 446, 58), 'c13_pvc'),
+    (2221, 4, (445, 28, 445, 51), 'c13_pvc'),
+    (2221, 4, (446, 28, 446, 58), 'c13_spec'),
+    (2221, 2, (590, 65, 590, 82), 'c13_ok'),
+    (2221, 0, (591, 25, 591, 63), 'B_C13_START'),
+    (2221, 0, (592, 25, 592, 59), 'B_C13_C2'),
+    (2221, 0, (593, 17, 594, 53), 'gen_C13'),
+    (2772, 0, (596, 1, 596, 8), 'C2'),
+    (2221, 0, (596, 16, 596, 30), 'NC*states + pairs_C2'),
+    (2221, 1, (596, 16, 596, 23), 'NC*states'),
+    (2221, 0, (597, 16, 597, 74), 'gen_C2'),
+    (2221, 0, (598, 16, 599, 68), 'gen_C2'),
+    (2221, 0, (600, 16, 600, 47), 'gen_C2'),
+    (2221, 0, (601, 16, 602, 35), 'gen_C2'),
+    (2772, 0, (604, 1, 604, 8), 'C3'),
+    (2221, 0, (604, 16, 604, 30), 'NC*states + pairs_C3'),
+    (2221, 1, (604, 16, 604, 23), 'NC*states'),
+    (2221, 0, (605, 19, 605, 50), 'gen_C3'),
+    (2221, 0, (606, 24, 606, 62), 'B_C3_START'),
+    (2221, 0, (607, 24, 607, 58), 'B_C3_C8'),
+    (2221, 0, (608, 16, 609, 52), 'gen_C3'),
+    (2772, 0, (611, 1, 611, 8), 'C8'),
+    (2221, 0, (611, 16, 611, 30), 'NC*states + pairs_C8'),
+    (2221, 1, (611, 16, 611, 23), 'NC*states'),
+    (2221, 0, (612, 19, 612, 46), 'gen_C8'),
+    (2221, 0, (613, 24, 613, 58), 'B_C8_C4'),
+    (2221, 0, (614, 24, 614, 58), 'B_C8_C6'),
+    (2221, 0, (615, 16, 616, 52), 'gen_C8'),
+    (2772, 0, (618, 1, 618, 8), 'C6'),
+    (2221, 0, (618, 16, 618, 30), 'NC*states + pairs_C6'),
+    (2221, 1, (618, 16, 618, 23), 'NC*states'),
+    (2221, 0, (619, 16, 627, 59), 'pairs_C6'),
+    (2221, 0, (628, 16, 629, 46), 'gen_C6'),
+    (2772, 0, (631, 1, 631, 8), 'C7'),
+    (2221, 0, (631, 16, 631, 30), 'NC*states + pairs_C7'),
+    (2221, 1, (631, 16, 631, 23), 'NC*states'),
+    (2221, 0, (632, 19, 632, 90), 'gen_C7'),
+    (2221, 1, (632, 19, 632, 46), 'gen_C7'),
+    (2221, 1, (632, 51, 632, 90), 'c7_ok'),
+    (2221, 0, (633, 24, 633, 62), 'B_C7_START'),
+    (2221, 0, (634, 24, 634, 58), 'B_C7_C4'),
+    (2221, 0, (635, 16, 636, 52), 'gen_C7'),
+    (2772, 0, (638, 1, 638, 8), 'C4'),
+    (2221, 0, (638, 16, 638, 30), 'NC*states + pairs_C4'),
+    (2221, 1, (638, 16, 638, 23), 'NC*states'),
+    (2221, 0, (639, 16, 640, 68), 'gen_C4'),
+    (2221, 1, (639, 23, 639, 66), 'gen_C4'),
+    (2221, 2, (639, 24, 639, 66), 'gen_C4'),
+    (2221, 3, (410, 22, 410, 59), 'gen_C4'),
+    (2221, 4, (410, 41, 410, 59), 'c4_iter'),
+    (2221, 4, (410, 31, 410, 38), 'gen_C4'),
+    (2221, 3, (639, 37, 639, 65), 'c4_iter'),
+    (2221, 0, (641, 16, 641, 47), 'gen_C4'),
+    (2221, 0, (642, 16, 643, 52), 'gen_C4'),
+    (2772, 0, (645, 1, 645, 8), 'C5'),
+    (2221, 0, (645, 16, 645, 30), 'NC*states + pairs_C5'),
+    (2221, 1, (645, 16, 645, 23), 'NC*states'),
+    (2221, 0, (646, 16, 646, 51), 'gen_C5'),
+    (2221, 0, (647, 16, 648, 52), 'gen_C5'),
+    (2772, 0, (655, 1, 655, 14), 'PVCStart'),
+    (2221, 0, (655, 22, 655, 42), 'NP*states + pairs_PVCStart'),
+    (2221, 1, (655, 22, 655, 29), 'NP*states'),
+    (2221, 0, (656, 22, 660, 73), 'gen_PVCStart'),
+    (2221, 0, (661, 22, 661, 64), 'gen_PVCStart'),
+    (2221, 0, (662, 22, 663, 52), 'gen_PVCStart'),
+    (2772, 0, (665, 1, 665, 19), 'PVCListedPVCs'),
+    (2221, 0, (665, 27, 665, 52), 'NP*states + pairs_PVCListedPVCs'),
+    (2221, 1, (665, 27, 665, 34), 'NP*states'),
+    (2221, 0, (666, 30, 667, 85), 'gen_PVCListedPVCs'),
+    (2221, 1, (666, 33, 666, 64), 'gen_PVCListedPVCs'),
+    (2221, 1, (667, 33, 667, 85), 'pvcl_ok'),
+    (2221, 2, (667, 33, 667, 80), 'pvcl_ok'),
+    (2221, 3, (667, 65, 667, 79), 'pvcl_objs'),
+    (2221, 4, (444, 22, 446, 58), 'pvcl_objs'),
+    (2221, 5, (444, 25, 444, 37), 'pvcl_objs'),
+    (2221, 5, (445, 25, 446, 58), 'pvcl_objs_pvc'),
+    (2221, 6, (445, 28, 445, 51), 'pvcl_objs_pvc'),
+    (2221, 6, (446, 28, 446, 58), 'pvcl_objs_spec'),
+    (2221, 4, (667, 78, 667, 78), 'pvcl_objs'),
+    (2221, 3, (667, 40, 667, 62), 'pvcl_ok'),
+    (2221, 2, (667, 84, 667, 85), 'pvcl_ok'),
+    (2221, 0, (668, 35, 668, 75), 'B_PVCL_START'),
+    (2221, 0, (669, 35, 669, 78), 'B_PVCL_HAVE'),
+    (2221, 0, (670, 27, 671, 72), 'gen_PVCListedPVCs'),
+    (2772, 0, (673, 1, 673, 17), 'PVCHavePVCs'),
+    (2221, 0, (673, 25, 673, 48), 'NP*states + pairs_PVCHavePVCs'),
+    (2221, 1, (673, 25, 673, 32), 'NP*states'),
+    (2221, 0, (674, 25, 686, 70), 'pairs_PVCHavePVCs'),
+    (2221, 0, (687, 25, 688, 55), 'gen_PVCHavePVCs'),
+    (2772, 0, (690, 1, 690, 13), 'PVCDone'),
+    (2221, 0, (690, 21, 690, 40), 'NP*states + pairs_PVCDone'),
+    (2221, 1, (690, 21, 690, 28), 'NP*states'),
+    (2221, 0, (691, 21, 691, 58), 'gen_PVCDone'),
+    (2221, 0, (692, 21, 693, 62), 'gen_PVCDone'),
+    (2772, 0, (698, 1, 698, 14), 'APIStart'),
+    (2221, 0, (698, 22, 698, 42), 'NS*states + en_APIStart'),
+    (2221, 1, (698, 22, 698, 29), 'NS*states'),
+    (2221, 0, (700, 33, 700, 57), 'B_API_CREATE + B_API_FORCE + B_API_GET + B_API_DELETE + B_API_UPDATE + B_API_ASSERT'),
+    (2221, 0, (702, 52, 702, 102), 'create_exists'),
+    (2221, 0, (703, 52, 703, 69), 'create_exists'),
+    (2221, 0, (704, 52, 704, 103), 'B_API_CREATE - create_exists'),
+    (2221, 0, (705, 52, 705, 99), 'B_API_CREATE - create_exists'),
+    (2221, 0, (706, 44, 706, 67), 'B_API_FORCE + B_API_GET + B_API_DELETE + B_API_UPDATE + B_API_ASSERT'),
+    (2221, 0, (707, 55, 707, 104), 'B_API_FORCE'),
+    (2221, 1, (707, 74, 707, 104), 'force_iter'),
+    (2221, 2, (390, 24, 390, 49), 'force_iter'),
+    (2221, 3, (390, 24, 390, 34), 'force_iter'),
+    (2221, 3, (390, 39, 390, 49), 'B_API_FORCE_REPLACE'),
+    (2221, 2, (707, 86, 707, 86), 'force_iter'),
+    (2221, 2, (707, 89, 707, 103), 'force_iter'),
+    (2221, 1, (707, 64, 707, 71), 'B_API_FORCE'),
+    (2221, 0, (708, 63, 713, 91), 'B_API_FORCE_REPLACE'),
+    (2775, 1, (708, 83, 713, 91), 'B_API_FORCE_REPLACE', None),
+    (2221, 2, (709, 75, 712, 79), 'force_setsz'),
+    (2221, 3, (709, 78, 709, 108), 'force_setsz'),
+    (2221, 4, (390, 24, 390, 49), 'force_setsz'),
+    (2221, 5, (390, 24, 390, 34), 'force_setsz'),
+    (2221, 5, (390, 39, 390, 49), 'force_same'),
+    (2221, 4, (709, 90, 709, 90), 'force_setsz'),
+    (2221, 4, (709, 93, 709, 107), 'force_setsz'),
+    (2221, 3, (710, 79, 710, 100), 'force_same'),
+    (2221, 3, (712, 79, 712, 79), 'force_setsz - force_same'),
+    (2221, 2, (713, 83, 713, 90), 'B_API_FORCE_REPLACE'),
+    (2221, 0, (714, 60, 714, 114), 'B_API_FORCE_CREATE'),
+    (2221, 0, (715, 52, 715, 99), 'B_API_FORCE'),
+    (2221, 0, (716, 55, 716, 76), 'B_API_GET + B_API_DELETE + B_API_UPDATE + B_API_ASSERT'),
+    (2221, 0, (717, 66, 717, 115), 'B_API_GET'),
+    (2221, 1, (717, 85, 717, 115), 'get_iter'),
+    (2221, 2, (390, 24, 390, 49), 'get_iter'),
+    (2221, 3, (390, 24, 390, 34), 'get_iter'),
+    (2221, 3, (390, 39, 390, 49), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 2, (717, 97, 717, 97), 'get_iter'),
+    (2221, 2, (717, 100, 717, 114), 'get_iter'),
+    (2221, 1, (717, 75, 717, 82), 'B_API_GET'),
+    (2221, 0, (718, 74, 720, 121), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 1, (718, 86, 720, 121), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 2, (718, 87, 718, 94), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 2, (718, 103, 719, 145), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 2, (718, 114, 719, 145), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 3, (719, 115, 719, 145), 'get_iter_found'),
+    (2221, 4, (390, 24, 390, 49), 'get_iter_found'),
+    (2221, 5, (390, 24, 390, 34), 'get_iter_found'),
+    (2221, 5, (390, 39, 390, 49), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 4, (719, 127, 719, 127), 'get_iter_found'),
+    (2221, 4, (719, 130, 719, 144), 'get_iter_found'),
+    (2221, 3, (718, 127, 718, 134), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 2, (720, 103, 720, 120), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 0, (721, 74, 726, 102), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2775, 1, (721, 94, 726, 102), 'B_API_GET - B_API_GET_NOTFOUND', None),
+    (2221, 2, (722, 86, 725, 90), 'get_setsz'),
+    (2221, 3, (722, 89, 722, 120), 'get_setsz'),
+    (2221, 4, (390, 24, 390, 49), 'get_setsz'),
+    (2221, 5, (390, 24, 390, 34), 'get_setsz'),
+    (2221, 5, (390, 39, 390, 49), 'get_same'),
+    (2221, 4, (722, 101, 722, 101), 'get_setsz'),
+    (2221, 4, (722, 104, 722, 119), 'get_setsz + get_same'),
+    (2221, 3, (723, 90, 723, 99), 'get_same'),
+    (2221, 3, (725, 90, 725, 90), 'get_setsz - get_same'),
+    (2221, 2, (726, 94, 726, 101), 'B_API_GET - B_API_GET_NOTFOUND'),
+    (2221, 0, (727, 74, 727, 124), 'B_API_GET_NOTFOUND'),
+    (2221, 0, (728, 74, 728, 91), 'B_API_GET_NOTFOUND'),
+    (2221, 0, (729, 66, 729, 90), 'B_API_DELETE + B_API_UPDATE + B_API_ASSERT'),
+    (2221, 0, (730, 74, 730, 135), 'B_API_DELETE'),
+    (2775, 1, (730, 86, 730, 135), 'B_API_DELETE', None),
+    (2221, 2, (730, 103, 730, 134), 'del_setsz'),
+    (2221, 3, (730, 104, 730, 134), 'del_setsz'),
+    (2221, 4, (390, 24, 390, 49), 'del_setsz'),
+    (2221, 5, (390, 24, 390, 34), 'del_setsz'),
+    (2221, 5, (390, 39, 390, 49), 'del_same'),
+    (2221, 4, (730, 116, 730, 116), 'del_setsz'),
+    (2221, 4, (730, 119, 730, 133), 'del_setsz'),
+    (2221, 2, (730, 93, 730, 100), 'B_API_DELETE'),
+    (2221, 0, (731, 74, 731, 121), 'B_API_DELETE'),
+    (2221, 0, (732, 77, 732, 101), 'B_API_UPDATE + B_API_ASSERT'),
+    (2221, 0, (733, 88, 733, 156), 'B_API_UPDATE'),
+    (2221, 1, (733, 108, 733, 155), 'upd_iter'),
+    (2221, 2, (733, 108, 733, 138), 'upd_iter'),
+    (2221, 3, (390, 24, 390, 49), 'upd_iter'),
+    (2221, 4, (390, 24, 390, 34), 'upd_iter'),
+    (2221, 4, (390, 39, 390, 49), 'upd_nmatch'),
+    (2221, 3, (733, 120, 733, 120), 'upd_iter'),
+    (2221, 3, (733, 123, 733, 137), 'upd_iter'),
+    (2221, 2, (733, 143, 733, 155), 'upd_nmatch'),
+    (2221, 1, (733, 97, 733, 104), 'B_API_UPDATE'),
+    (2221, 0, (734, 96, 736, 131), 'B_API_UPDATE_OK'),
+    (2221, 1, (734, 108, 736, 131), 'B_API_UPDATE_OK'),
+    (2221, 2, (734, 108, 734, 157), 'B_API_UPDATE_OK'),
+    (2221, 3, (734, 125, 734, 156), 'upd_setsz'),
+    (2221, 4, (734, 126, 734, 156), 'upd_setsz'),
+    (2221, 5, (390, 24, 390, 49), 'upd_setsz'),
+    (2221, 6, (390, 24, 390, 34), 'upd_setsz'),
+    (2221, 6, (390, 39, 390, 49), 'upd_same'),
+    (2221, 5, (734, 138, 734, 138), 'upd_setsz'),
+    (2221, 5, (734, 141, 734, 155), 'upd_setsz'),
+    (2221, 3, (734, 115, 734, 122), 'B_API_UPDATE_OK'),
+    (2775, 2, (736, 108, 736, 131), 'B_API_UPDATE_OK', '2*B_API_UPDATE_OK'),
+    (2221, 0, (737, 96, 737, 143), 'B_API_UPDATE_OK'),
+    (2221, 0, (738, 96, 738, 146), 'B_API_UPDATE_ERR'),
+    (2221, 0, (739, 96, 739, 113), 'B_API_UPDATE_ERR'),
+    (2221, 0, (742, 85, 743, 108), 'B_API_ASSERT'),
+    (2221, 0, (699, 37, 699, 50), 'NS*states'),
+    (2775, 1, (441, 19, 441, 73), 'NS*states', 'NS*states + B_API_CREATE + B_API_FORCE + B_API_GET + B_API_DELETE + B_API_UPDATE + B_API_ASSERT'),
+    (2221, 2, (441, 43, 441, 72), 'NS*cov_req'),
+    (2221, 2, (441, 26, 441, 40), 'NS*states'),
+    (2221, 0, (744, 28, 744, 49), 'B_API_CREATE + B_API_FORCE + B_API_GET + B_API_DELETE + B_API_UPDATE + B_API_ASSERT'),
+    (2221, 0, (746, 33, 747, 88), 'B_API_LIST'),
+    (2221, 1, (746, 49, 747, 88), 'B_API_LIST'),
+    (2221, 2, (746, 50, 746, 61), 'B_API_LIST'),
+    (2221, 2, (746, 70, 746, 125), 'B_API_LIST'),
+    (2775, 2, (746, 82, 746, 125), 'B_API_LIST', None),
+    (2221, 3, (746, 99, 746, 124), 'list_setsz'),
+    (2221, 3, (746, 89, 746, 96), 'B_API_LIST'),
+    (2221, 2, (747, 70, 747, 87), 'B_API_LIST'),
+    (2221, 0, (748, 33, 753, 61), 'B_API_LIST'),
+    (2775, 1, (748, 53, 753, 61), 'B_API_LIST', None),
+    (2221, 2, (749, 45, 752, 49), 'list_setsz'),
+    (2221, 3, (749, 48, 749, 74), 'list_setsz'),
+    (2221, 3, (750, 49, 750, 58), 'list_match'),
+    (2221, 3, (752, 49, 752, 49), 'list_setsz - list_match'),
+    (2221, 2, (753, 53, 753, 60), 'B_API_LIST'),
+    (2221, 0, (745, 37, 745, 54), 'NS*states'),
+    (2775, 1, (442, 23, 442, 85), 'NS*states', 'NS*states + B_API_LIST'),
+    (2221, 2, (442, 51, 442, 84), 'NS*cov_lreq'),
+    (2221, 2, (442, 30, 442, 48), 'NS*states'),
+    (2221, 0, (754, 28, 754, 45), 'B_API_LIST'),
+    (2221, 0, (755, 22, 755, 59), 'gen_APIStart'),
+    (2221, 0, (756, 22, 756, 74), 'gen_APIStart'),
+    (2774, 0, (776, 1, 776, 6), 'TypeOK'),
+    (2221, 0, (778, 5, 781, 72), 'states'),
+    (2221, 1, (778, 8, 778, 45), 'states'),
+    (2221, 2, (778, 27, 778, 45), 'cov_api'),
+    (2221, 2, (778, 17, 778, 24), 'states'),
+    (2221, 1, (780, 8, 780, 60), 'states'),
+    (2221, 2, (780, 34, 780, 60), 'cov_req'),
+    (2221, 2, (780, 17, 780, 31), 'states'),
+    (2221, 1, (781, 8, 781, 72), 'states'),
+    (2221, 2, (781, 38, 781, 72), 'cov_lreq'),
+    (2221, 3, (433, 5, 436, 29), 'cov_lreq'),
+    (2221, 4, (433, 8, 433, 44), 'cov_lreq'),
+    (2221, 4, (434, 8, 435, 39), 'cov_lreq'),
+    (2221, 5, (434, 25, 435, 39), 'cov_objs'),
+    (2221, 5, (434, 17, 434, 22), 'cov_lreq'),
+    (2221, 4, (436, 8, 436, 29), 'cov_lreq'),
+    (2221, 3, (781, 57, 781, 71), 'cov_lreq'),
+    (2221, 2, (781, 17, 781, 35), 'states'),
+    (2774, 0, (787, 1, 787, 14), 'OnlyOneVersion'),
+    (2221, 0, (788, 5, 789, 51), 'states'),
+    (2221, 1, (788, 29, 789, 51), 'cov_api2'),
+    (2221, 2, (788, 32, 788, 38), 'cov_api2'),
+    (2221, 2, (789, 32, 789, 51), 'cov_api2 - cov_api'),
+    (2221, 1, (788, 19, 788, 26), 'states'),
+)
+# MC.out lines of the 2775 messages whose cost figure is not derived: the
+# count is printed alone
+COVERAGE_COST_UNKNOWN = (675, 783, 828, 966, 981)
+
+
+def coverage_values(r, cov: Dict[str, int], procs=(1, 1, 1)) -> List[tuple]:
+    """COVERAGE_LINES evaluated for one run: (code, depth, span, name, count,
+    cost) per row; count / cost None where the message has none."""
+    nc, np_, ns = procs
+    env = dict(cov)
+    env.update({"gen_" + a: v for a, v in r.act_gen.items()})
+    env.update(init=r.init, P=nc + np_ + ns, NC=nc, NP=np_, NS=ns)
+    out = []
+    for row in COVERAGE_LINES:
+        code, depth, span, formula = row[:4]
+        if code == 2773:
+            out.append((code, 0, span, formula, r.init, r.init))
+        elif code == 2772:
+            out.append((code, 0, span, formula, r.act_gen[formula], r.act_dist[formula]))
+        elif code == 2774:
+            out.append((code, 0, span, formula, None, None))
+        else:
+            cost = row[4] if code == 2775 else None
+            out.append((code, depth, span, None, eval(formula, {"__builtins__": {}}, env),
+                        None if cost is None else eval(cost, {"__builtins__": {}}, env)))
+    return out
+
+
+def coverage_messages(r, cov: Dict[str, int], procs=(1, 1, 1)) -> List[tuple]:
+    """The coverage block between 2201 and 2202 with expression-level
+    coverage: (code, body) in MC.out's order."""
+    out = []
+    for code, depth, span, name, count, cost in coverage_values(r, cov, procs):
+        l1, c1, l2, c2 = span
+        if code in (2773, 2772):
+            out.append((code, f"{span_text(name, span)}: {cost}:{count}"))
+        elif code == 2774:
+            out.append((code, span_text(name, span)))
+        else:
+            body = f"  {'|' * depth}line {l1}, col {c1} to line {l2}, col {c2} of module KubeAPI: {count}"
+            out.append((code, body if cost is None else f"{body}:{cost}"))
+    return out
 
 
 def span_text(name: str, span) -> str:
@@ -252,11 +684,14 @@ def tstamp(t: float) -> str:
 
 
 def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = None,
-             engine: str = "", ngpus: int = 1, symmetry: Optional[str] = None) -> List[tuple]:
+             engine: str = "", ngpus: int = 1, symmetry: Optional[str] = None,
+             coverage: Optional[Dict[str, int]] = None, procs=(1, 1, 1)) -> List[tuple]:
     """TLC -tool messages (code, class, body) for one check's result, in the
-    order of the reference run (MC.out:1-1108).  SANY's (2220/2219) and the
-    expression-level coverage (2221) are not produced: there is no TLA+ front
-    end here."""
+    order of the reference run (MC.out:1-1108).  coverage (a
+    CheckResult.coverage of a model with procs = (nc, np, ns)) adds the
+    expression-level lines (2221, 2775, 2774) between the per-action ones, as
+    TLC's -coverage prints them.  SANY's messages (2220/2219) are not
+    produced: there is no TLA+ front end here."""
     out = []
     add = lambda code, text, cls=0: out.append((code, cls, text))  # noqa: E731
     add(2262, f"kubecheck (TLC-compatible counts) {engine}".rstrip())
@@ -288,9 +723,13 @@ def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = 
         for num, body in zip(blocks[0::2], blocks[1::2]):
             add(2217, f"{num}: {body.strip()}", 4)
     add(2201, f"The coverage statistics at {tstamp(t_end)}")
-    add(2773, f"{span_text('Init', INIT_SPAN)}: {r.init}:{r.init}")
-    for name, span in ACTION_SPANS.items():
-        add(2772, f"{span_text(name, span)}: {r.act_dist[name]}:{r.act_gen[name]}")
+    if coverage is not None:
+        for code, body in coverage_messages(r, coverage, procs):
+            add(code, body)
+    else:
+        add(2773, f"{span_text('Init', INIT_SPAN)}: {r.init}:{r.init}")
+        for name, span in ACTION_SPANS.items():
+            add(2772, f"{span_text(name, span)}: {r.act_dist[name]}:{r.act_gen[name]}")
     add(2202, "End of statistics.")
     add(2200, f"Progress({r.depth}) at {tstamp(t_end)}: {g:,} states generated ({int(g / minutes):,} s/min), "
               f"{d:,} distinct states found ({int(d / minutes):,} ds/min), {r.queue_left:,} states left on queue.")
@@ -401,9 +840,28 @@ def split_simulate(argv: List[str]):
     return rest, sim, num
 
 
+def split_coverage(argv: List[str]):
+    """Take TLC's `-coverage [minutes]` out of argv: (rest, coverage?).  TLC's
+    argument is the interval of its periodic reports, which are not printed
+    here: an integer after the flag is accepted and ignored."""
+    rest, cov = [], False
+    i = 0
+    while i < len(argv):
+        if argv[i] != "-coverage":
+            rest.append(argv[i])
+            i += 1
+            continue
+        cov = True
+        i += 1
+        if i < len(argv) and argv[i].isdigit():
+            i += 1
+    return rest, cov
+
+
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, simulate, num = split_simulate(argv)
+    argv, coverage = split_coverage(argv)
     ap = argparse.ArgumentParser(prog="kubecheck.tlc", description=__doc__.split("\n\n")[0])
     ap.add_argument("-depth", type=int, default=SIM_DEFAULT_DEPTH,
                     help="-simulate: the most states in a behaviour (TLC's default 100)")
@@ -427,6 +885,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                     help="temporal properties: WF_vars(Next) (the default) or weak fairness of every process")
     a = ap.parse_args(argv)
     a.simulate, a.num = simulate, (num if num is not None else SIM_DEFAULT_WALKS)
+    a.coverage = coverage
+    if simulate and coverage:
+        raise CfgError("-coverage with -simulate: expression-level coverage is counted by the BFS only")
     if simulate and a.fairness is not None:
         raise CfgError("-fairness goes with a PROPERTY list; -simulate checks no temporal property")
     a.fairness = a.fairness or "next"
@@ -449,7 +910,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     tla_path = os.path.join(os.path.dirname(os.path.abspath(cfg_path)), f"{a.spec}.tla")
     defs = parse_defs(open(tla_path).read()) if os.path.exists(tla_path) else {}
     parsed = parse_cfg(open(cfg_path).read(), defs)
-    kw, props = check_from_cfg(parsed, a.simulate)
+    kw, props = check_from_cfg(parsed, a.simulate, a.coverage)
 
     import kubecheck
 
@@ -467,12 +928,12 @@ def main(argv: Optional[List[str]] = None) -> int:
                                             kubecheck.load().kc_build_info().decode()):
             print(msg(code, body, cls, a.tool), flush=True)
         return 0 if r.error is None else 12
-    with kubecheck.ModelChecker(mc_cfg) as mc:
+    with kubecheck.ModelChecker(mc_cfg, coverage=a.coverage) as mc:
         r = mc.run()
         prob = None if (a.nocheckfps or r.error is not None) else mc.check_fps()[1]
     t1 = t0 + r.seconds
     out = messages(r, t0, t1, prob, kubecheck.load().kc_build_info().decode(), kubecheck.device_count(),
-                   parsed["symmetry"])
+                   parsed["symmetry"], coverage=r.coverage if a.coverage else None, procs=(a.nc, a.np, a.ns))
     if not props or r.error is not None:
         for code, cls, body in out:
             print(msg(code, body, cls, a.tool), flush=True)
