@@ -371,6 +371,101 @@ int kc_engine_narrow_times(kc_engine *e, double *ms, uint64_t *launches, uint64_
  * *prob_out = 1/min_gap. */
 int kc_engine_check_fps(kc_engine *e, uint64_t *min_gap_out, double *prob_out);
 
+/* ---------------------------------------------------------- Checkpoint */
+/* Checkpoint and recover (TLC's -checkpoint / -recover; DESIGN.md section
+ * 4.10) for the single-GPU in-HBM engine: both claim modes, narrow and wide
+ * levels, the deferred and the materialising frontier, with or without
+ * keep_trace and symmetry.  Not with seen_hbm_bytes, frontier_hbm_bytes or
+ * trace_host, not with coverage on (-EINVAL and a kc_last_error text), and
+ * not for the sharded loop, simulation or liveness, which have no such calls.
+ *
+ * A checkpoint is the state at the top of a BFS level: that level's frontier,
+ * the seen-set as bare fingerprints (old claim words are never read again, so
+ * it restores into a table of any size and either slot layout), the
+ * cumulative counters and, with keep_trace, the trace file.  A recovered run
+ * reports cumulative results, as if it had never stopped.
+ *
+ * The file is DIR/checkpoint.kc, written as checkpoint.kc.tmp, fsynced and
+ * renamed, so a writer that dies leaves the previous checkpoint intact.  It
+ * holds little-endian u64 words: a header of 64 words, then the sections.
+ *
+ *   word  0      magic 0x54504B434542554B ("KUBECKPT" as bytes)
+ *   word  1      format version (1)
+ *   word  2      header length in words (64)
+ *   word  3      file length in bytes
+ *   words 4-13   nc, np, ns, can_fail, can_timeout, check_deadlock, variant,
+ *                invariants, effective symmetry mask (bits whose process set
+ *                has fewer than two members cleared), state_words
+ *   word  14     keep_trace (0 / 1)
+ *   word  15     claim mode that wrote it (kc_result.claim_mode; informational)
+ *   words 16-20  level, level_gidx (states before this level), n (frontier
+ *                width), cand (successors of the frontier, exact), cand_total
+ *   words 21-24  init, distinct, nlevels, peak_frontier
+ *   word  25     number of sections (5)
+ *   words 26-45  per section {offset in bytes, length in bytes, sum, xor};
+ *                all four 0 for a section the checkpoint does not carry
+ *   words 46-61  0
+ *   words 62-63  (sum, xor) of words 0-61
+ *
+ * A checksum is the pair (sum mod 2^64, xor) of the u64 words it covers.
+ * Sections (offsets are multiples of 8, at or after byte 512, none overlapping):
+ *   0 COUNTERS      level_width[nlevels], act_gen[22], act_dist[22],
+ *                   outdeg_hist[16], fpset probes of the wide levels, settles,
+ *                   candidate overflow records, fpset probes of the narrow levels
+ *   1 FRONTIER      n x state_words packed states, in the engine's FIFO order
+ *   2 FPS           `distinct` fingerprint words, in any order
+ *   3 TRACE_PARENT  (level_gidx + n) x u64 parent index (~0 for an Init state);
+ *                   with keep_trace only
+ *   4 TRACE_ORD     (level_gidx + n) x u8 successor ordinal, zero-padded to a
+ *                   multiple of 8 bytes; with keep_trace only
+ * distinct = level_gidx + n, nlevels = level, and the level widths add up to
+ * distinct with n the last. */
+#define KC_CKPT_SECTIONS 5
+/* (a struct tag, not a typedef: the function below has the same name) */
+struct kc_checkpoint_info {
+  uint64_t version, file_bytes;
+  int nc, np, ns, can_fail, can_timeout, check_deadlock, variant, invariants;
+  int symmetry;            /* the effective mask */
+  int state_words, keep_trace, claim_mode;
+  int level, nlevels;
+  uint64_t level_gidx, n, cand, cand_total;
+  uint64_t init, distinct, peak_frontier;
+  uint64_t section_offset[KC_CKPT_SECTIONS], section_bytes[KC_CKPT_SECTIONS];
+  uint64_t section_sum[KC_CKPT_SECTIONS], section_xor[KC_CKPT_SECTIONS];
+};
+typedef struct {
+  const char *dir;
+  int every_levels;        /* > 0: checkpoint at the top of level L when L - L0 is a positive
+                              multiple of it (L0 = 1, or the recovered level) */
+  double every_seconds;    /* > 0: ... or when this much wall time has passed since the last one */
+  uint64_t stage_bytes;    /* pinned staging per buffer, two buffers; 0 = 64 MiB; >= 4096 */
+} kc_checkpoint_options;
+/* Read and fully validate DIR/checkpoint.kc on the host (no GPU): the header,
+ * the section table and every section's checksum, streamed.  -ENOENT: no
+ * file; -EINVAL: not a checkpoint (magic) or an unknown version; -EIO:
+ * truncated, inconsistent, or failing a checksum. */
+int kc_checkpoint_info(const char *dir, struct kc_checkpoint_info *out);
+/* Write the state the last kc_engine_run left, when that run stopped at
+ * max_levels with err_kind == 0 and queue_left > 0 (-EINVAL otherwise). */
+int kc_engine_checkpoint(kc_engine *e, const char *dir);
+/* Make kc_engine_run itself checkpoint at level tops (see the options); each
+ * checkpoint replaces the one before.  A deferred frontier is materialised
+ * first, which changes no result.  NULL = off: the engine then allocates and
+ * launches exactly what it does without this call.  Also takes stage_bytes
+ * for kc_engine_checkpoint and kc_engine_recover (dir may then be NULL with
+ * both periods 0). */
+int kc_engine_set_checkpoint(kc_engine *e, const kc_checkpoint_options *opt);
+/* Validate DIR/checkpoint.kc against the engine's model and arm the next
+ * kc_engine_run only: it starts at the checkpoint's level instead of Init
+ * (max_levels keeps its absolute meaning); a later run starts from Init
+ * again.  -EINVAL names the first model field that differs (an engine with
+ * keep_trace = 1 cannot take a checkpoint without trace sections; the reverse
+ * is fine); -EIO on a bad file.  The table is sized as the larger of
+ * fpset_slots and what the engine's growth rule keeps for `distinct` entries.
+ * The armed run fails with -EIO if a restored fingerprint is not new to the
+ * table or a section uploaded to the device fails its checksum there. */
+int kc_engine_recover(kc_engine *e, const char *dir);
+
 /* --------------------------------------------------- Sharded (multi-GPU) */
 /* Fingerprint-owner-sharded BFS, one process per GPU (replaces TLC's
  * single-host worker pool; TLC's own distributed mode is off in Model_1,
@@ -807,6 +902,22 @@ int kc_spill_selftest(int kind, int np, const uint64_t *a, uint64_t na, const ui
 int kc_emit_selftest(int kind, const kc_model_config *cfg, const uint64_t *par, uint64_t npar, const uint64_t *a,
                      uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *out, uint64_t nout, uint64_t *res,
                      uint64_t nres);
+
+/* ------------------------------------------------ Checkpoint streams (tests) */
+/* Device harness for the checkpoint streams (csrc/ckpt_selftest.hip) on a
+ * table of exactly nslots slots; layout 0 = 16-B {fp, ~claim} slots, 1 = the
+ * compact table's u64 words (nslots even).  stage_bytes as in
+ * kc_checkpoint_options.  stats_out has 4 words.
+ * kind 0: in = a table image of n words (2 per slot, or 1); k_ckpt_pack over
+ *   it in windows of `window` slots (0 = what a staging buffer takes);
+ *   out[0 .. count) = the dense fingerprint stream (room for nslots words),
+ *   stats_out = [count, sum, xor, words the sink received].
+ * kind 1: in = n fingerprints; they go into an empty table through the
+ *   recovery's list inserts, at most `window` per launch (0 = a staging
+ *   buffer's worth); out = the table image, stats_out = [inserts that were not
+ *   new, sum, xor of the list as uploaded, n].  Test-only. */
+int kc_ckpt_selftest(int kind, int layout, uint64_t nslots, const uint64_t *in, uint64_t n, uint64_t window,
+                     uint64_t stage_bytes, uint64_t *out, uint64_t *stats_out);
 
 /* ------------------------------------------------- Probe primitives (tests) */
 /* Device harness for the seen-set probe loops (csrc/probe_selftest.hip): runs

@@ -40,6 +40,12 @@ class EngineBase {
   // counters from the next run on; the last run's sums
   virtual int set_coverage(bool on) = 0;
   virtual int coverage(uint64_t* out, int cap) const = 0;
+  // checkpoint / recover: write the state the last run
+  // stopped with; checkpoint from inside run(); arm the next run to start
+  // from a checkpoint
+  virtual int checkpoint(const char* dir) = 0;
+  virtual int set_checkpoint(const kc_checkpoint_options* opt) = 0;
+  virtual int recover(const char* dir) = 0;
   void set_timing(bool on) { timing_ = on ? 1 : 0; }
   void kernel_times(double* ms, uint64_t* launches) const {
     for (int k = 0; k < KK_COUNT; ++k) {

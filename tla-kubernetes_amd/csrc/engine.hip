@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/kubecheck.h"
+#include "ckpt.h"
 #include "claim_launch.h"
 #include "coldset.h"
 #include "cover.h"
@@ -261,7 +262,8 @@ class EngineT final : public EngineBase {
   // level found them), so error reports and every count come from the path
   // that checks each new state where it is emitted.  When that cannot be
   // done exactly (a rehash since, KC_DEFER_REDO=0) the whole run is redone
-  // from Init on the exact path.
+  // from Init on the exact path.  (A run recovered from a checkpoint: from
+  // the checkpoint, which run_once restores again.)
   int run(kc_result* res) override {
     defer_now_ = defer_;
     int rc = run_once(res);
@@ -270,8 +272,9 @@ class EngineT final : public EngineBase {
       defer_now_ = false;
       rc = run_once(res);
       res->defer_fallback = 1;
-      res->defer_redo_level = 1;
+      res->defer_redo_level = rec_armed_ ? (uint64_t)rec_info_.level : 1;
     }
+    rec_armed_ = false;              // (recover() arms one run)
     cover_valid_ = cover_on_ && rc == 0 && res->err_kind == 0;
     return rc;
   }
@@ -287,6 +290,10 @@ class EngineT final : public EngineBase {
     }
     if (on && (spill_ || queued_ || cfg_.trace_host || ablate_)) {
       set_error("kc_engine_set_coverage: not with seen_hbm_bytes, frontier_hbm_bytes or trace_host");
+      return -EINVAL;
+    }
+    if (on && (ck_on_ || rec_armed_)) {
+      set_error("kc_engine_set_coverage: not with checkpointing (a checkpoint holds no coverage sums)");
       return -EINVAL;
     }
     cover_on_ = on;
@@ -347,6 +354,325 @@ class EngineT final : public EngineBase {
     bool mat = true;
     double ratio = 1.0;
   };
+
+  // ---- checkpoint / recover (ckpt.h).  A checkpoint is the
+  // top of a level with its states materialised in cur_: the cursor, the
+  // run's totals, the cumulative counters, the ClaimSet's fingerprints and
+  // the trace file.  Nothing here runs, and nothing is allocated, unless one
+  // of the three calls below was made.
+  const char* ckpt_refusal() const {
+    if (spill_ || queued_ || cfg_.trace_host) return "not with seen_hbm_bytes, frontier_hbm_bytes or trace_host";
+    if (cover_on_) return "not with coverage on (a checkpoint holds no coverage sums)";
+    if (ablate_) return "not with KC_ABLATE";
+    return nullptr;
+  }
+  int set_checkpoint(const kc_checkpoint_options* opt) override {
+    if (!opt) {
+      ck_on_ = false;
+      ck_every_ = 0;
+      ck_seconds_ = 0;
+      ck_stage_bytes_ = 0;
+      return 0;
+    }
+    const bool periodic = opt->every_levels > 0 || opt->every_seconds > 0;
+    if (const char* why = ckpt_refusal()) {
+      set_error("kc_engine_set_checkpoint: %s", why);
+      return -EINVAL;
+    }
+    if (periodic && (!opt->dir || !opt->dir[0])) {
+      set_error("kc_engine_set_checkpoint: no directory");
+      return -EINVAL;
+    }
+    if (opt->stage_bytes && opt->stage_bytes < CKPT_STAGE_MIN) {
+      set_error("kc_engine_set_checkpoint: stage_bytes %llu below %llu", (unsigned long long)opt->stage_bytes,
+                (unsigned long long)CKPT_STAGE_MIN);
+      return -EINVAL;
+    }
+    ck_on_ = periodic;
+    ck_every_ = std::max(opt->every_levels, 0);
+    ck_seconds_ = opt->every_seconds > 0 ? opt->every_seconds : 0;
+    ck_stage_bytes_ = opt->stage_bytes;
+    ck_dir_ = opt->dir ? opt->dir : "";
+    return 0;
+  }
+  int checkpoint(const char* dir) override {
+    if (!dir || !dir[0]) {
+      set_error("kc_engine_checkpoint: no directory");
+      return -EINVAL;
+    }
+    if (const char* why = ckpt_refusal()) {
+      set_error("kc_engine_checkpoint: %s", why);
+      return -EINVAL;
+    }
+    if (!stop_valid_) {
+      set_error("kc_engine_checkpoint: the last run did not stop at max_levels with states left and no error");
+      return -EINVAL;
+    }
+    return write_checkpoint(dir, stop_cur_, stop_totals_);
+  }
+  int recover(const char* dir) override {
+    if (!dir || !dir[0]) {
+      set_error("kc_engine_recover: no directory");
+      return -EINVAL;
+    }
+    if (const char* why = ckpt_refusal()) {
+      set_error("kc_engine_recover: %s", why);
+      return -EINVAL;
+    }
+    CkptFileSource src;
+    const std::string path = ckpt_path(dir);
+    int rc = src.open(path);
+    if (rc) {
+      set_error("kc_engine_recover: %s: %s", path.c_str(), rc == -ENOENT ? "no such file" : "cannot open");
+      return rc;
+    }
+    std::string err;
+    struct kc_checkpoint_info h;
+    rc = ckpt_validate(src, &h, &err);
+    if (rc) {
+      set_error("kc_engine_recover: %s: %s", path.c_str(), err.c_str());
+      return rc;
+    }
+    const int mine[] = {cfg_.nc, cfg_.np, cfg_.ns, cfg_.can_fail != 0, cfg_.can_timeout != 0, cfg_.check_deadlock != 0,
+                        cfg_.variant, cfg_.invariants & 7, sym_effective(cfg_.nc, cfg_.np, cfg_.symmetry), M::W};
+    const int theirs[] = {h.nc, h.np, h.ns, h.can_fail, h.can_timeout, h.check_deadlock, h.variant, h.invariants,
+                          h.symmetry, h.state_words};
+    static const char* names[] = {"nc", "np", "ns", "can_fail", "can_timeout", "check_deadlock", "variant",
+                                  "invariants", "symmetry", "state_words"};
+    for (int k = 0; k < 10; ++k)
+      if (mine[k] != theirs[k]) {
+        set_error("kc_engine_recover: the checkpoint has %s = %d, the engine %d", names[k], theirs[k], mine[k]);
+        return -EINVAL;
+      }
+    if (cfg_.keep_trace && !h.keep_trace) {
+      set_error("kc_engine_recover: the checkpoint has keep_trace = 0 (no trace sections), the engine 1");
+      return -EINVAL;
+    }
+    rec_dir_ = dir;
+    rec_info_ = h;
+    rec_armed_ = true;
+    return 0;
+  }
+
+  // the totals of a run so far that a checkpoint carries besides the counters
+  struct RunTotals {
+    uint64_t init = 0, distinct = 0, peak = 0;
+    int nlevels = 0;
+    std::vector<uint64_t> widths;
+  };
+  static RunTotals totals_of(const kc_result* res) {
+    RunTotals t;
+    t.init = res->init;
+    t.distinct = res->distinct;
+    t.peak = res->peak_frontier;
+    t.nlevels = res->nlevels;
+    t.widths.assign(res->level_width, res->level_width + res->nlevels);
+    return t;
+  }
+  bool ckpt_due(int level) const {
+    if (ck_every_ > 0 && level > ck_l0_ && (level - ck_l0_) % ck_every_ == 0) return true;
+    return ck_seconds_ > 0 &&
+           std::chrono::duration<double>(std::chrono::steady_clock::now() - ck_last_).count() >= ck_seconds_;
+  }
+  // run()'s own checkpoint at the top of level c.level: a deferred frontier
+  // is materialised first, as the narrow path and the level capture do
+  int ckpt_now(const kc_result* res, LevelCursor& c) {
+    if (!c.mat) {
+      KC_TRY(materialize(c));
+      c.mat = true;
+      KC_TRY(counter_snap(c.level - 1));     // (k_materialize counted the states' actions)
+      pc_valid_ = false;
+    }
+    KC_TRY(write_checkpoint(ck_dir_.c_str(), c, totals_of(res)));
+    ck_last_ = std::chrono::steady_clock::now();
+    return 0;
+  }
+
+  int write_checkpoint(const char* dir, const LevelCursor& c, const RunTotals& t) {
+    static_assert(sizeof(State) == (size_t)M::W * 8, "a packed state is W words");
+    KC_HIP_TRY(hipSetDevice(cfg_.device));
+    const auto tw0 = std::chrono::steady_clock::now();
+    KC_TRY(ck_stage_.setup(ck_stage_bytes_));
+    std::string err;
+    CkptWriter wr;
+    const int orc = wr.open(dir, &err);
+    if (orc) {
+      set_error("checkpoint: %s", err.c_str());
+      return orc;
+    }
+    const CkptSink sink = [&wr](const uint64_t* w, uint64_t n) -> int {
+      const int r = wr.append(w, n);
+      if (r) set_error("checkpoint: write failed: %s", strerror(errno));
+      return r;
+    };
+    // COUNTERS: the widths, then the striped totals summed
+    KC_HIP_TRY(hipStreamSynchronize(st_));
+    if (!ck_ctr_) ck_ctr_.reset(new Counters);
+    KC_HIP_TRY(hipMemcpy(ck_ctr_.get(), d_ctr_, sizeof(Counters), hipMemcpyDeviceToHost));
+    std::vector<uint64_t> cw(t.widths);
+    for (int a = 0; a < A_COUNT; ++a) cw.push_back(ck_ctr_->act_gen(a));
+    for (int a = 0; a < A_COUNT; ++a) cw.push_back(ck_ctr_->act_dist(a));
+    for (int b = 0; b < OUTDEG_BINS; ++b) cw.push_back(ck_ctr_->outdeg(b));
+    cw.push_back(ck_ctr_->probes());
+    cw.push_back(ck_ctr_->settles());
+    cw.push_back(ck_ctr_->cand_ovf());
+    cw.push_back(narrow_probes_);
+    static_assert(2 * A_COUNT + OUTDEG_BINS + 4 == CKPT_COUNTER_TAIL, "the COUNTERS section's fixed part");
+    wr.begin(CS_COUNTERS);
+    KC_TRY(sink(cw.data(), cw.size()));
+    wr.begin(CS_FRONTIER);
+    KC_TRY(ckpt_download(cur_.p, c.n * sizeof(State), ck_stage_, st_, sink));
+    // FPS: the device's count and checksum of the stream against the run's
+    // count and what reached the file
+    wr.begin(CS_FPS);
+    uint64_t nfp = 0;
+    CkptSum dsum;
+    double pack_ms = 0;
+    const auto tp0 = std::chrono::steady_clock::now();
+    KC_TRY(ckpt_pack_fps(cs_, 0, ck_stage_, st_, sink, &nfp, &dsum, cfg_.verbose ? &pack_ms : nullptr));
+    const double fps_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count();
+    if (nfp != t.distinct || nfp != cs_.count) {
+      set_error("checkpoint: the seen-set holds %llu fingerprints, the run counted %llu", (unsigned long long)nfp,
+                (unsigned long long)t.distinct);
+      return -EIO;
+    }
+    if (!(dsum == wr.sum(CS_FPS))) {
+      set_error("checkpoint: the fingerprint stream's checksum changed between the device and the file");
+      return -EIO;
+    }
+    const uint64_t states = c.level_gidx + c.n;
+    if (cfg_.keep_trace) {
+      wr.begin(CS_TRACE_PARENT);
+      KC_TRY(ckpt_download(tf_.parent(), states * 8, ck_stage_, st_, sink));
+      wr.begin(CS_TRACE_ORD);
+      KC_TRY(ckpt_download(tf_.ord(), states, ck_stage_, st_, sink));
+    }
+    uint64_t w[CKPT_HEADER_WORDS] = {};
+    w[CW_NC] = (uint64_t)cfg_.nc, w[CW_NP] = (uint64_t)cfg_.np, w[CW_NS] = (uint64_t)cfg_.ns;
+    w[CW_CAN_FAIL] = cfg_.can_fail != 0, w[CW_CAN_TIMEOUT] = cfg_.can_timeout != 0;
+    w[CW_CHECK_DEADLOCK] = cfg_.check_deadlock != 0;
+    w[CW_VARIANT] = (uint64_t)cfg_.variant;
+    w[CW_INVARIANTS] = (uint64_t)(cfg_.invariants & 7);
+    w[CW_SYMMETRY] = (uint64_t)sym_effective(cfg_.nc, cfg_.np, cfg_.symmetry);
+    w[CW_STATE_WORDS] = (uint64_t)M::W;
+    w[CW_KEEP_TRACE] = cfg_.keep_trace != 0;
+    w[CW_CLAIM_MODE] = first_claim_ ? 1 : 0;
+    w[CW_LEVEL] = (uint64_t)c.level, w[CW_LEVEL_GIDX] = c.level_gidx, w[CW_N] = c.n;
+    w[CW_CAND] = c.cand, w[CW_CAND_TOTAL] = c.cand_total;
+    w[CW_INIT] = t.init, w[CW_DISTINCT] = t.distinct, w[CW_NLEVELS] = (uint64_t)t.nlevels;
+    w[CW_PEAK_FRONTIER] = t.peak;
+    const int frc = wr.finish(w, &err);
+    if (frc) set_error("checkpoint: %s", err.c_str());
+    if (cfg_.verbose && !frc)
+      fprintf(stderr, "kubecheck: checkpoint at level %d: %llu bytes, %llu states; k_ckpt_pack %.3f ms over %llu table "
+                      "bytes; FPS section %.3f s; whole write %.3f s\n",
+              c.level, (unsigned long long)wr.file_bytes(), (unsigned long long)t.distinct, pack_ms,
+              (unsigned long long)(cs_.nslots * cs_.slot_bytes()), fps_s,
+              std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count());
+    return frc;
+  }
+
+  // The armed run's start, in place of seed_init: c and res as the
+  // checkpointed run had them at the top of its level.
+  int restore_run(kc_result* res, LevelCursor& c) {
+    const struct kc_checkpoint_info& h = rec_info_;
+    CkptFileSource src;
+    const std::string path = ckpt_path(rec_dir_.c_str());
+    std::string err;
+    struct kc_checkpoint_info now;
+    if (src.open(path) || ckpt_parse_header(src, &now, &err) || now.file_bytes != h.file_bytes ||
+        now.level != h.level || now.distinct != h.distinct ||
+        memcmp(now.section_sum, h.section_sum, sizeof h.section_sum) != 0) {
+      set_error("kubecheck: %s is gone or changed since kc_engine_recover", path.c_str());
+      return -EIO;
+    }
+    KC_TRY(ck_stage_.setup(ck_stage_bytes_));
+    // one section's words, and the device's checksum of it against the header's
+    auto feed_of = [&](int s) {
+      return CkptFeed([&src, &h, s](uint64_t* dst, uint64_t at, uint64_t n) -> int {
+        if (src.read(h.section_offset[s] + at * 8, dst, n * 8)) return 0;
+        set_error("kubecheck: checkpoint read failed");
+        return -EIO;
+      });
+    };
+    auto same = [&](int s, const CkptSum& got) -> int {
+      if (got.sum == h.section_sum[s] && got.x == h.section_xor[s]) return 0;
+      set_error("kubecheck: checkpoint section %d fails its checksum on the device", s);
+      return -EIO;
+    };
+    // the Init states: path_to starts from them
+    std::vector<State> init;
+    std::vector<uint64_t> fps;
+    (void)init_list(init, fps);
+    init_states_ = init;
+    // the seen-set: the table seed_init would make, grown for the checkpoint's
+    // fingerprints by the engine's own rule, filled by the list inserts
+    const uint64_t fp_slots = cfg_.fpset_slots ? cfg_.fpset_slots : (1ull << 20);
+    if (cs_.t && cs_.capacity() >= fp_slots) {
+      KC_TRY(cs_.clear(st_));
+    } else {
+      KC_TRY(cs_.init(fp_slots, st_));
+    }
+    KC_TRY(cs_.reserve(h.distinct, st_));
+    uint64_t bad = 0;
+    CkptSum got;
+    KC_TRY(ckpt_restore_fps(cs_, h.distinct, 0, ck_stage_, st_, feed_of(CS_FPS), &bad, &got));
+    if (bad) {
+      set_error("kubecheck: %llu of the checkpoint's fingerprints were not new to the table", (unsigned long long)bad);
+      return -EIO;
+    }
+    KC_TRY(same(CS_FPS, got));
+    cs_.count = h.distinct;
+    hot_count_ = h.distinct;
+    // the frontier and the trace file
+    KC_TRY(cur_.grow(h.n, st_));
+    KC_TRY(ckpt_upload(cur_.p, h.n * M::W, ck_stage_, st_, feed_of(CS_FRONTIER), &got));
+    KC_TRY(same(CS_FRONTIER, got));
+    const uint64_t states = h.level_gidx + h.n;
+    KC_TRY(tf_.grow(false, cfg_.keep_trace ? states + h.cand + 16 : h.init + h.cand, st_, false));
+    if (cfg_.keep_trace) {
+      KC_TRY(ckpt_upload(tf_.parent(), states, ck_stage_, st_, feed_of(CS_TRACE_PARENT), &got));
+      KC_TRY(same(CS_TRACE_PARENT, got));
+      // (the padding of the last word is part of the section: cap >= states + 16)
+      KC_TRY(ckpt_upload(tf_.ord(), h.section_bytes[CS_TRACE_ORD] / 8, ck_stage_, st_, feed_of(CS_TRACE_ORD), &got));
+      KC_TRY(same(CS_TRACE_ORD, got));
+    }
+    // the counters: the saved totals in stripe 0, zero in the rest
+    std::vector<uint64_t> cw(h.section_bytes[CS_COUNTERS] / 8);
+    KC_TRY(feed_of(CS_COUNTERS)(cw.data(), 0, cw.size()));
+    const uint64_t* q = cw.data() + h.nlevels;
+    if (!ck_ctr_) ck_ctr_.reset(new Counters);
+    memset(ck_ctr_.get(), 0, sizeof(Counters));
+    CtrStripe& s0 = ck_ctr_->s[0];
+    for (int a = 0; a < A_COUNT; ++a) s0.act_gen[a] = q[a];
+    for (int a = 0; a < A_COUNT; ++a) s0.act_dist[a] = q[A_COUNT + a];
+    for (int b = 0; b < OUTDEG_BINS; ++b) s0.outdeg[b] = q[2 * A_COUNT + b];
+    q += 2 * A_COUNT + OUTDEG_BINS;
+    s0.probes = q[0];
+    s0.settles = q[1];
+    s0.cand_ovf = q[2];
+    narrow_probes_ = q[3];
+    s0.next_cand = h.cand_total;
+    KC_HIP_TRY(hipMemcpyAsync(d_ctr_, ck_ctr_.get(), sizeof(Counters), hipMemcpyHostToDevice, st_));
+    if (d_ovf_cnt_) KC_HIP_TRY(hipMemsetAsync(d_ovf_cnt_, 0, 8, st_));
+    if (csum_) KC_HIP_TRY(hipMemsetAsync(csum_, 0, csum_.cap * sizeof(uint32_t), st_));
+    // (a deferred-frontier redo from this level needs the previous level's counters)
+    if (defer_now_) KC_TRY(counter_snap(h.level - 1));
+    KC_HIP_TRY(hipStreamSynchronize(st_));
+    res->init = h.init;
+    res->distinct = h.distinct;
+    res->peak_frontier = h.peak_frontier;
+    res->nlevels = h.nlevels;
+    for (int L = 0; L < h.nlevels; ++L) res->level_width[L] = cw[L];
+    c = LevelCursor{};
+    c.n = h.n;
+    c.level_gidx = h.level_gidx;
+    c.cand = h.cand;
+    c.cand_total = h.cand_total;
+    c.level = h.level;
+    return 0;
+  }
+
   // What a level's launches share, fixed when its buffers are sized.
   struct LevelPlan {
     bool dfr = false;            // this level runs deferred (emits links, not states)
@@ -365,8 +691,10 @@ class EngineT final : public EngineBase {
     KC_TRY(cover_begin());
     LevelCursor c;
     std::vector<State> init;
-    int rc = seed_init(res, c, init);
+    int rc = rec_armed_ ? restore_run(res, c) : seed_init(res, c, init);
     if (rc) return rc < 0 ? rc : 0;
+    ck_l0_ = c.level;
+    ck_last_ = t0_;
 
     if (queued_) return run_queued(res, c.n, c.cand, init);
 
@@ -383,6 +711,7 @@ class EngineT final : public EngineBase {
     pc_valid_ = false;                 // pc_prev_ holds the previous frontier's plans
     while (c.n > 0) {
       if (cfg_.max_levels && c.level >= cfg_.max_levels) break;
+      if (ck_on_ && ckpt_due(c.level)) KC_TRY(ckpt_now(res, c));
       if (narrow_on_ && c.n <= (uint64_t)NARROW_MAX &&
           (c.mat || (double)c.n * c.ratio <= 1.25 * (double)NARROW_CAND_MAX)) {
         rc = narrow_levels(res, c);
@@ -409,6 +738,13 @@ class EngineT final : public EngineBase {
     last_level_ = res->nlevels;
     last_n_ = c.n;
     finish(res, c.n);
+    // what kc_engine_checkpoint writes: the level's top as this run left it
+    if (c.n && !spill_) {
+      stop_cur_ = c;
+      stop_cur_.mat = true;
+      stop_totals_ = totals_of(res);
+      stop_valid_ = true;
+    }
     if (ablate_) KC_TRY(ablate_report());
     return 0;
   }
@@ -420,6 +756,7 @@ class EngineT final : public EngineBase {
     res->err_action = res->err_self = res->err_invariant = -1;
     res->claim_mode = first_claim_ ? 1 : 0;
     trace_.clear();
+    stop_valid_ = false;
     narrow_probes_ = 0;
     for (auto& t : ktime_ms_) t = 0;
     ev_kind_.clear();
@@ -438,11 +775,10 @@ class EngineT final : public EngineBase {
   // Init state violates an invariant (reported).
   // (under symmetry the fingerprint is the orbit's: of the Init states of
   // one orbit the first is kept, the others count as generated only)
-  int seed_init(kc_result* res, LevelCursor& c, std::vector<State>& init) {
-    const int ni_all = M::num_init();
-    std::vector<uint64_t> fps;
+  // the Init states kept (one per fingerprint), their fingerprints and successor count
+  uint64_t init_list(std::vector<State>& init, std::vector<uint64_t>& fps) const {
     uint64_t cand = 0;
-    for (int k = 0; k < ni_all; ++k) {
+    for (int k = 0; k < M::num_init(); ++k) {
       State s0;
       M::init_state(k, s0, cfg_.variant);
       const uint64_t fp0 = M::fingerprint(s0);
@@ -451,6 +787,12 @@ class EngineT final : public EngineBase {
       fps.push_back(fp0);
       cand += (uint64_t)M::plan(s0, flags_).total;
     }
+    return cand;
+  }
+  int seed_init(kc_result* res, LevelCursor& c, std::vector<State>& init) {
+    const int ni_all = M::num_init();
+    std::vector<uint64_t> fps;
+    const uint64_t cand = init_list(init, fps);
     const int ni = (int)init.size();
     // the seen-set allocation is kept across runs (cleared each run), like a
     // TLC FPSet pre-sized with -fpmem; it grows by rehash when needed
@@ -541,6 +883,11 @@ class EngineT final : public EngineBase {
     if (capture_level_ >= c.level + 1 && (stop == 0 || capture_level_ - 1 < stop)) stop = capture_level_ - 1;
     // coverage: one level per run, counted from cur_ before the run expands it
     if (cover_on_ && (stop == 0 || c.level + 1 < stop)) stop = c.level + 1;
+    // a checkpoint by levels: the run stops at the top of the next level due
+    if (ck_on_ && ck_every_ > 0) {
+      const int due = c.level + ck_every_ - (c.level - ck_l0_) % ck_every_;
+      if (stop == 0 || due < stop) stop = due;
+    }
     const int level0 = c.level;
     const uint64_t n0 = c.n;
     NarrowRun nr;
@@ -1875,6 +2222,22 @@ class EngineT final : public EngineBase {
   std::vector<State> init_states_, trace_, captured_;
   uint64_t last_n_ = 0;
   int last_level_ = 0;
+  // checkpoint / recover: run()'s own checkpoints (set_checkpoint), the level
+  // top the last run stopped at (checkpoint) and the armed recovery (recover)
+  bool ck_on_ = false;
+  int ck_every_ = 0, ck_l0_ = 1;
+  double ck_seconds_ = 0;
+  uint64_t ck_stage_bytes_ = 0;
+  std::string ck_dir_;
+  std::chrono::steady_clock::time_point ck_last_;
+  CkptStage ck_stage_;
+  std::unique_ptr<Counters> ck_ctr_;     // host copy of the counters, out and in
+  LevelCursor stop_cur_;
+  RunTotals stop_totals_;
+  bool stop_valid_ = false;
+  std::string rec_dir_;
+  struct kc_checkpoint_info rec_info_ {};
+  bool rec_armed_ = false;
 };
 
 template <class M>
@@ -2001,6 +2364,21 @@ int kc_engine_set_coverage(kc_engine* e, int on) {
 int kc_engine_coverage(kc_engine* e, uint64_t* out, int cap) {
   if (!e) { set_error("kc_engine_coverage: NULL"); return -EINVAL; }
   return e->impl->coverage(out, cap);
+}
+
+int kc_engine_checkpoint(kc_engine* e, const char* dir) {
+  if (!e) { set_error("kc_engine_checkpoint: NULL"); return -EINVAL; }
+  return e->impl->checkpoint(dir);
+}
+
+int kc_engine_set_checkpoint(kc_engine* e, const kc_checkpoint_options* opt) {
+  if (!e) { set_error("kc_engine_set_checkpoint: NULL"); return -EINVAL; }
+  return e->impl->set_checkpoint(opt);
+}
+
+int kc_engine_recover(kc_engine* e, const char* dir) {
+  if (!e) { set_error("kc_engine_recover: NULL"); return -EINVAL; }
+  return e->impl->recover(dir);
 }
 
 int kc_engine_narrow_times(kc_engine* e, double* ms, uint64_t* launches, uint64_t* levels) {

@@ -25,19 +25,22 @@ All compute runs in libkubecheck.so (HIP, gfx950).  There is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Union
 
 import numpy as np
 
-from ._lib import (ACTIONS, ERR_KINDS, FAIRNESS, INVARIANTS, LIVE_KINDS, PROPERTIES, SIM_KINDS, KcLiveConfig,
+from ._lib import (ACTIONS, CKPT_SECTIONS, ERR_KINDS, FAIRNESS, INVARIANTS, LIVE_KINDS, PROPERTIES, SIM_KINDS,
+                   KcCheckpointInfo, KcCheckpointOptions, KcLiveConfig,
                    KcLiveResult, KcModelConfig, KcResult, KcSimConfig,
                    KcSimResult, KcSqueueConfig, KcSqueueStats, KubecheckError,
                    check, load)
 
 __all__ = ["ModelConfig", "ModelChecker", "CheckResult", "FPSet", "StateQueue", "Spec",
            "Simulator", "SimResult", "SIM_KINDS", "LivenessChecker", "LiveResult", "PROPERTIES", "FAIRNESS",
-           "KubecheckError", "ACTIONS", "load", "device_count", "stress_fps_dev", "stress_fp"]
+           "KubecheckError", "ACTIONS", "load", "device_count", "stress_fps_dev", "stress_fp",
+           "CheckpointInfo", "checkpoint_info"]
 
 
 def device_count() -> int:
@@ -206,6 +209,53 @@ def _result(r: KcResult) -> CheckResult:
         claim_mode=CLAIM_MODES.get(r.claim_mode, str(r.claim_mode)))
 
 
+@dataclass
+class CheckpointInfo:
+    """The header of a checkpoint file (include/kubecheck.h "Checkpoint")."""
+    version: int
+    file_bytes: int
+    nc: int
+    np: int
+    ns: int
+    can_fail: bool
+    can_timeout: bool
+    check_deadlock: bool
+    variant: int
+    invariants: int
+    symmetry: int                  # the effective mask
+    state_words: int
+    keep_trace: bool
+    claim_mode: str                # the claims of the run that wrote it
+    level: int                     # the BFS level whose top was saved
+    nlevels: int
+    level_gidx: int
+    n: int                         # frontier width
+    cand: int
+    cand_total: int
+    init: int
+    distinct: int
+    peak_frontier: int
+    sections: Dict[str, Dict[str, int]]   # name -> offset, bytes, sum, xor (absent sections left out)
+
+
+def checkpoint_info(dir: str) -> CheckpointInfo:
+    """Read and fully validate DIR/checkpoint.kc on the host (no GPU needed).
+    Raises KubecheckError: -2 no file, -22 not a checkpoint or an unknown
+    version, -5 truncated, inconsistent or failing a checksum."""
+    r = KcCheckpointInfo()
+    check("kc_checkpoint_info", load().kc_checkpoint_info(os.fsencode(dir), C.byref(r)))
+    sections = {name: {"offset": int(r.section_offset[i]), "bytes": int(r.section_bytes[i]),
+                       "sum": int(r.section_sum[i]), "xor": int(r.section_xor[i])}
+                for i, name in enumerate(CKPT_SECTIONS) if r.section_bytes[i]}
+    return CheckpointInfo(
+        version=r.version, file_bytes=r.file_bytes, nc=r.nc, np=r.np, ns=r.ns, can_fail=bool(r.can_fail),
+        can_timeout=bool(r.can_timeout), check_deadlock=bool(r.check_deadlock), variant=r.variant,
+        invariants=r.invariants, symmetry=r.symmetry, state_words=r.state_words, keep_trace=bool(r.keep_trace),
+        claim_mode=CLAIM_MODES.get(r.claim_mode, str(r.claim_mode)), level=r.level, nlevels=r.nlevels,
+        level_gidx=r.level_gidx, n=r.n, cand=r.cand, cand_total=r.cand_total, init=r.init, distinct=r.distinct,
+        peak_frontier=r.peak_frontier, sections=sections)
+
+
 class ModelChecker:
     """BFS safety checker (TLC's ModelChecker for this spec) on one GPU."""
 
@@ -260,6 +310,31 @@ class ModelChecker:
         check("kc_engine_level_tuples", self._lib.kc_engine_level_tuples(
             self._h, level, out.ctypes.data_as(C.POINTER(C.c_uint64)), n))
         return out
+
+    # ---- checkpoint / recover (TLC's -checkpoint / -recover; include/kubecheck.h "Checkpoint")
+    def checkpoint(self, dir: str) -> None:
+        """Write DIR/checkpoint.kc from the state the last run() left; that
+        run must have stopped at max_levels with states on the queue."""
+        check("kc_engine_checkpoint", self._lib.kc_engine_checkpoint(self._h, os.fsencode(dir)))
+
+    def recover(self, dir: str) -> None:
+        """Arm the next run() to start from DIR/checkpoint.kc instead of Init.
+        What that run reports is cumulative, as if it had never stopped."""
+        check("kc_engine_recover", self._lib.kc_engine_recover(self._h, os.fsencode(dir)))
+
+    def set_checkpoint(self, dir: Optional[str], every_levels: int = 0, every_seconds: float = 0.0,
+                       stage_bytes: int = 0) -> None:
+        """Make run() checkpoint into DIR every `every_levels` levels and / or
+        every `every_seconds` seconds (each replaces the one before);
+        stage_bytes sizes the two pinned staging buffers of every checkpoint
+        and recovery of this checker.  dir=None with no period switches run()'s
+        checkpoints off."""
+        if dir is None and not every_levels and not every_seconds and not stage_bytes:
+            check("kc_engine_set_checkpoint", self._lib.kc_engine_set_checkpoint(self._h, None))
+            return
+        self._ckpt_dir = os.fsencode(dir) if dir is not None else None
+        opt = KcCheckpointOptions(self._ckpt_dir, int(every_levels), float(every_seconds), int(stage_bytes))
+        check("kc_engine_set_checkpoint", self._lib.kc_engine_set_checkpoint(self._h, C.byref(opt)))
 
     def kernel_times(self):
         ms = (C.c_double * 4)()

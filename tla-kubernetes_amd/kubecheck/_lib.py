@@ -68,6 +68,27 @@ class KcResult(C.Structure):
     ]
 
 
+KC_CKPT_SECTIONS = 5
+CKPT_SECTIONS = ("COUNTERS", "FRONTIER", "FPS", "TRACE_PARENT", "TRACE_ORD")
+
+
+class KcCheckpointInfo(C.Structure):
+    _fields_ = [("version", C.c_uint64), ("file_bytes", C.c_uint64),
+                ("nc", C.c_int), ("np", C.c_int), ("ns", C.c_int), ("can_fail", C.c_int), ("can_timeout", C.c_int),
+                ("check_deadlock", C.c_int), ("variant", C.c_int), ("invariants", C.c_int), ("symmetry", C.c_int),
+                ("state_words", C.c_int), ("keep_trace", C.c_int), ("claim_mode", C.c_int),
+                ("level", C.c_int), ("nlevels", C.c_int),
+                ("level_gidx", C.c_uint64), ("n", C.c_uint64), ("cand", C.c_uint64), ("cand_total", C.c_uint64),
+                ("init", C.c_uint64), ("distinct", C.c_uint64), ("peak_frontier", C.c_uint64),
+                ("section_offset", C.c_uint64 * KC_CKPT_SECTIONS), ("section_bytes", C.c_uint64 * KC_CKPT_SECTIONS),
+                ("section_sum", C.c_uint64 * KC_CKPT_SECTIONS), ("section_xor", C.c_uint64 * KC_CKPT_SECTIONS)]
+
+
+class KcCheckpointOptions(C.Structure):
+    _fields_ = [("dir", C.c_char_p), ("every_levels", C.c_int), ("every_seconds", C.c_double),
+                ("stage_bytes", C.c_uint64)]
+
+
 KC_SIM_MAX_DEPTH = 65535
 # how a simulated walk ended (kc_sim_walks / kc_sim_replay): ERR_KINDS' 1-3, then
 SIM_KINDS = {0: "running", 1: "assertion", 2: "invariant", 3: "deadlock", 4: "depth", 5: "terminated"}
@@ -195,6 +216,12 @@ SIGNATURES = [
     ("kc_engine_kernel_times", C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
     ("kc_engine_narrow_times", C.c_int, [_P, C.POINTER(C.c_double), _U64P, _U64P]),
     ("kc_engine_check_fps", C.c_int, [_P, _U64P, C.POINTER(C.c_double)]),
+    ("kc_checkpoint_info", C.c_int, [C.c_char_p, C.POINTER(KcCheckpointInfo)]),
+    ("kc_engine_checkpoint", C.c_int, [_P, C.c_char_p]),
+    ("kc_engine_set_checkpoint", C.c_int, [_P, C.POINTER(KcCheckpointOptions)]),
+    ("kc_engine_recover", C.c_int, [_P, C.c_char_p]),
+    ("kc_ckpt_selftest", C.c_int, [C.c_int, C.c_int, C.c_uint64, _U64P, C.c_uint64, C.c_uint64, C.c_uint64, _U64P,
+                                   _U64P]),
     ("kc_shard_create", C.c_int, [C.POINTER(KcModelConfig), C.c_int, C.c_int, C.POINTER(_P)]),
     ("kc_shard_destroy", None, [_P]),
     ("kc_shard_init", C.c_int, [_P, _U64P]),

@@ -3,7 +3,9 @@
     python -m kubecheck.tlc [-config MC.cfg] [-deadlock] [-tool] [-nc N -np N -ns N]
                             [-variant V] [-workers N] [-fp K]
                             [-simulate [num=N]] [-depth D] [-seed S] [-continue]
-                            [-fairness next|process] [-coverage [minutes]] [MC]
+                            [-fairness next|process] [-coverage [minutes]]
+                            [-checkpoint MINUTES] [-checkpointlevels N] [-metadir DIR]
+                            [-recover DIR] [MC]
 
 Reads the same inputs as the reference's toolbox run: a TLC model config
 (KubeAPI.toolbox/Model_1/MC.cfg:1-16 — CONSTANT assignments, either direct
@@ -73,6 +75,22 @@ process counts the lines are the same expressions with self sets of NC clients
 and NP controllers; TLC pins none of them.  After a run that ends in an error
 the block has the per-action lines only.  -coverage with -simulate, a PROPERTY
 list or SYMMETRY is an error.  Without the flag nothing changes.
+
+Checkpoint and recover (DESIGN.md §4.10): `-checkpoint MINUTES` (TLC's flag;
+0 = none, as in TLC) makes the BFS write a checkpoint into `-metadir DIR`
+(TLC's flag; default: `states` next to the .cfg) whenever that much time has
+passed, `-checkpointlevels N` (kubecheck's own, as -fairness is: a run that
+takes milliseconds cannot be cut by minutes) every N levels; each checkpoint
+replaces the one before.  `-recover DIR` (TLC's flag) starts the search from
+DIR's checkpoint instead of the initial states and reports cumulative
+results.  Under -tool a run that wrote a checkpoint prints TLC's 2195
+("Checkpointing of run ...") and 2196 ("Checkpointing completed at ...") once,
+for the last one, and a recovered run prints 2197 ("Starting recovery from
+checkpoint ...") and 2198 ("Recovery completed. N states examined. M states
+on queue.") in place of the initial-state messages.  The reference holds no
+checkpoint output: the codes and wording are recalled from TLC's message
+table and claim no match.  These flags together with -simulate, a PROPERTY
+list or -coverage are an error.
 
 `-fairness process` checks the properties under weak
 fairness of every process (PlusCal's `fair process`; a .cfg cannot say this,
@@ -189,13 +207,17 @@ def model_from_cfg(cfg: dict) -> dict:
     return kw
 
 
-def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False):
+def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, checkpointing: bool = False):
     """model_from_cfg for a cfg that may list temporal properties: (ModelConfig
     kwargs, the PROPERTY names in cfg order).  The names must be kubecheck's
-    PROPERTIES; simulation mode checks none.  coverage: -coverage was given."""
+    PROPERTIES; simulation mode checks none.  coverage: -coverage was given;
+    checkpointing: one of -checkpoint, -checkpointlevels, -recover was."""
     from ._lib import PROPERTIES
 
     props = list(cfg["properties"])
+    if checkpointing and props:
+        raise CfgError("-checkpoint / -recover with a PROPERTY list: a checkpoint holds the BFS's state, "
+                       "not the liveness graph")
     if coverage and simulate:
         raise CfgError("-coverage with -simulate: expression-level coverage is counted by the BFS only")
     if coverage and props:
@@ -685,13 +707,16 @@ def tstamp(t: float) -> str:
 
 def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = None,
              engine: str = "", ngpus: int = 1, symmetry: Optional[str] = None,
-             coverage: Optional[Dict[str, int]] = None, procs=(1, 1, 1)) -> List[tuple]:
+             coverage: Optional[Dict[str, int]] = None, procs=(1, 1, 1), recovered=None,
+             checkpointed=None) -> List[tuple]:
     """TLC -tool messages (code, class, body) for one check's result, in the
     order of the reference run (MC.out:1-1108).  coverage (a
     CheckResult.coverage of a model with procs = (nc, np, ns)) adds the
     expression-level lines (2221, 2775, 2774) between the per-action ones, as
     TLC's -coverage prints them.  SANY's messages (2220/2219) are not
-    produced: there is no TLA+ front end here."""
+    produced: there is no TLA+ front end here.  recovered =
+    (dir, CheckpointInfo) of a run started with -recover; checkpointed = (dir,
+    CheckpointInfo, time) of the last checkpoint the run wrote."""
     out = []
     add = lambda code, text, cls=0: out.append((code, cls, text))  # noqa: E731
     add(2262, f"kubecheck (TLC-compatible counts) {engine}".rstrip())
@@ -699,8 +724,15 @@ def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = 
               f"(kubecheck ClaimSet FPSet, HBM StateQueue)."
               + (f" Symmetry set: {symmetry}." if symmetry else ""))
     add(2185, f"Starting... ({tstamp(t_start)})")
-    add(2189, "Computing initial states...")
-    add(2190, f"Finished computing initial states: {r.init} distinct states generated at {tstamp(t_start)}.")
+    if recovered is not None:
+        add(2197, f"Starting recovery from checkpoint {recovered[0]}/")
+        add(2198, f"Recovery completed. {recovered[1].distinct} states examined. {recovered[1].n} states on queue.")
+    else:
+        add(2189, "Computing initial states...")
+        add(2190, f"Finished computing initial states: {r.init} distinct states generated at {tstamp(t_start)}.")
+    if checkpointed is not None:
+        add(2195, f"Checkpointing of run {checkpointed[0]}")
+        add(2196, f"Checkpointing completed at ({tstamp(checkpointed[2])})")
     d, g = r.distinct, r.generated
     minutes = max(t_end - t_start, 1e-9) / 60.0
     if r.error is None:
@@ -883,9 +915,21 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                     help="skip the 'based on the actual fingerprints' estimate (a sort of the seen-set)")
     ap.add_argument("-fairness", choices=("next", "process"), default=None,
                     help="temporal properties: WF_vars(Next) (the default) or weak fairness of every process")
+    ap.add_argument("-checkpoint", type=float, default=0.0, metavar="MINUTES",
+                    help="checkpoint whenever this many minutes have passed (TLC flag; 0 = none)")
+    ap.add_argument("-checkpointlevels", type=int, default=0, metavar="N", help="checkpoint every N BFS levels")
+    ap.add_argument("-metadir", default=None, help="where the checkpoint goes (TLC flag)")
+    ap.add_argument("-recover", default=None, metavar="DIR", help="start from DIR's checkpoint (TLC flag)")
     a = ap.parse_args(argv)
     a.simulate, a.num = simulate, (num if num is not None else SIM_DEFAULT_WALKS)
     a.coverage = coverage
+    if a.checkpoint < 0 or a.checkpointlevels < 0:
+        raise CfgError("-checkpoint / -checkpointlevels: expected a number >= 0")
+    a.checkpointing = bool(a.checkpoint > 0 or a.checkpointlevels > 0 or a.recover)
+    if a.checkpointing and simulate:
+        raise CfgError("-checkpoint / -recover with -simulate: a random walk has nothing to take up again")
+    if a.checkpointing and coverage:
+        raise CfgError("-checkpoint / -recover with -coverage: a checkpoint holds no coverage sums")
     if simulate and coverage:
         raise CfgError("-coverage with -simulate: expression-level coverage is counted by the BFS only")
     if simulate and a.fairness is not None:
@@ -910,7 +954,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     tla_path = os.path.join(os.path.dirname(os.path.abspath(cfg_path)), f"{a.spec}.tla")
     defs = parse_defs(open(tla_path).read()) if os.path.exists(tla_path) else {}
     parsed = parse_cfg(open(cfg_path).read(), defs)
-    kw, props = check_from_cfg(parsed, a.simulate, a.coverage)
+    try:
+        kw, props = check_from_cfg(parsed, a.simulate, a.coverage, a.checkpointing)
+    except CfgError as e:
+        if not a.checkpointing:
+            raise
+        print(f"Error: {e}", file=sys.stderr)
+        return 1
 
     import kubecheck
 
@@ -928,12 +978,31 @@ def main(argv: Optional[List[str]] = None) -> int:
                                             kubecheck.load().kc_build_info().decode()):
             print(msg(code, body, cls, a.tool), flush=True)
         return 0 if r.error is None else 12
+    recovered = checkpointed = None
+    metadir = a.metadir or a.recover or os.path.join(os.path.dirname(os.path.abspath(cfg_path)), "states")
     with kubecheck.ModelChecker(mc_cfg, coverage=a.coverage) as mc:
+        try:
+            if a.recover:
+                mc.recover(a.recover)
+                recovered = (a.recover.rstrip("/"), kubecheck.checkpoint_info(a.recover))
+            if a.checkpoint > 0 or a.checkpointlevels > 0:
+                os.makedirs(metadir, exist_ok=True)
+                mc.set_checkpoint(metadir, every_levels=a.checkpointlevels, every_seconds=a.checkpoint * 60.0)
+        except kubecheck.KubecheckError as e:
+            print(f"Error: {e}", file=sys.stderr)
+            return 1
         r = mc.run()
         prob = None if (a.nocheckfps or r.error is not None) else mc.check_fps()[1]
     t1 = t0 + r.seconds
+    # the last checkpoint this run wrote, if any
+    ck_file = os.path.join(metadir, "checkpoint.kc")
+    if (a.checkpoint > 0 or a.checkpointlevels > 0) and os.path.exists(ck_file) and os.path.getmtime(ck_file) >= t0 - 1:
+        info = kubecheck.checkpoint_info(metadir)
+        if recovered is None or info.level > recovered[1].level:
+            checkpointed = (metadir.rstrip("/"), info, os.path.getmtime(ck_file))
     out = messages(r, t0, t1, prob, kubecheck.load().kc_build_info().decode(), kubecheck.device_count(),
-                   parsed["symmetry"], coverage=r.coverage if a.coverage else None, procs=(a.nc, a.np, a.ns))
+                   parsed["symmetry"], coverage=r.coverage if a.coverage else None, procs=(a.nc, a.np, a.ns),
+                   recovered=recovered, checkpointed=checkpointed)
     if not props or r.error is not None:
         for code, cls, body in out:
             print(msg(code, body, cls, a.tool), flush=True)
