@@ -903,6 +903,43 @@ int kc_emit_selftest(int kind, const kc_model_config *cfg, const uint64_t *par, 
                      uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *out, uint64_t nout, uint64_t *res,
                      uint64_t nres);
 
+/* ------------------------------------------ k_claim and the settle passes (tests) */
+/* One launch set of k_claim (csrc/engine_kernels.h) over n parents and a
+ * seen-set image of exactly nslots slots, with the product's launch spelling
+ * (csrc/claim_selftest.hip).  The data rules are kc_emit_selftest's: u64 words,
+ * sections uploaded as given and copied back whole behind KC_EMIT_FORE guard
+ * elements, every index checked on the host first (-EINVAL with or without a
+ * GPU, -ENODEV only for good input).  cfg: nc = ns = 1, np 1 to 3 (kind 0 also
+ * nc = np = 1, ns = 0); variant, invariants and the constants apply.
+ * kind 0: k_claim<M>, then the engine's three settle launches; 1: first-claim
+ * on 16-B slots; 2: first-claim on the compact table (nslots even); 3: the
+ * sharded k_claim<M, 0, true, 1> with record staging, then the settle launches
+ * under the rank's claim keys.
+ * par = [n, base, level (the successors'), check_deadlock, spread, nslots,
+ *   world, rank, flags, nprev, stage_cap, aft]; flags: 1 = the deferred
+ *   frontier (kinds 0-2), 2 = with prev_counts, 4 = with csum (kinds 1, 2).
+ *   Kinds 0-2: world 1, rank 0, stage_cap 0; kind 3: world 2 to 8, base 0.
+ * a = n packed parents (na = n * state words; an Assert parent is legal), b
+ *   unused; deferred: na = 0 and b = nprev packed states of the previous
+ *   frontier (raising no Assert), then link[n] (parent << 8 | position, inside
+ *   the previous frontier and below the parent's successor count).
+ * table = the image, in and out: {fp, ~claim} per slot, or the compact table's
+ *   fp words; all zero = empty.  nslots >= stored + the frontier's successors
+ *   + 1.
+ * out = 12 sections, each KC_EMIT_FORE guards + its elements + aft guards:
+ *   newmask[n], rcount[tiles], tile_total / ttot[tiles], csum[ceil(tiles / 64)]
+ *   (flag 4, else empty), df.out[(base + n) states] and counts_out[base + n]
+ *   (deferred, else empty), and for kind 3 (else empty) repmask[n],
+ *   cnt[world][n], tcnt[world][tiles], stoff[tiles], the staging buffer
+ *   (stage_cap records, raw words), the same records unpacked (state words,
+ *   then the key; the harness writes these on the host).  tiles = ceil(n / 256).
+ * res = [err_key, overflow, probes, settles, cand_ovf, next_cand, defer_flags,
+ *   defer_inv_n, the overflow list's count, stage_cur, act_gen[22],
+ *   act_dist[22]].  Test-only. */
+int kc_claim_selftest(int kind, const kc_model_config *cfg, const uint64_t *par, uint64_t npar, const uint64_t *a,
+                      uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *table, uint64_t ntable, uint64_t *out,
+                      uint64_t nout, uint64_t *res, uint64_t nres);
+
 /* ------------------------------------------------ Checkpoint streams (tests) */
 /* Device harness for the checkpoint streams (csrc/ckpt_selftest.hip) on a
  * table of exactly nslots slots; layout 0 = 16-B {fp, ~claim} slots, 1 = the
@@ -963,6 +1000,9 @@ int kc_cover_count(void);
 const char *kc_cover_name(int i);
 /* Fingerprint of the packed form of a canonical tuple. */
 int kc_spec_fingerprint(const kc_model_config *cfg, const uint64_t *tuple, uint64_t *fp_out);
+/* The same with the owner projection of the sharded path in its top bits
+ * (M::fingerprint<1>): what kc_shard_owner takes. */
+int kc_spec_fingerprint_own(const kc_model_config *cfg, const uint64_t *tuple, uint64_t *fp_out);
 /* Self-check of the kernels' incremental fingerprint: the number of
  * successors of `tuple` whose fingerprint_succ differs from a full
  * fingerprint (0 expected), <0 on error. */

@@ -242,6 +242,17 @@ int kc_spec_fingerprint(const kc_model_config* cfg, const uint64_t* tuple, uint6
   });
 }
 
+int kc_spec_fingerprint_own(const kc_model_config* cfg, const uint64_t* tuple, uint64_t* fp) {
+  if (!cfg || !tuple || !fp) { set_error("kc_spec_fingerprint_own: NULL"); return -EINVAL; }
+  return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {
+    using M = decltype(m);
+    typename M::State s;
+    if (!M::from_tuple(tuple, s)) { set_error("kc_spec_fingerprint_own: bad tuple"); return -EINVAL; }
+    *fp = M::template fingerprint<1>(s);
+    return 0;
+  });
+}
+
 int kc_spec_permute(const kc_model_config* cfg, const uint64_t* tuple, const int* perm, uint64_t* out) {
   if (!cfg || !tuple || !perm || !out) { set_error("kc_spec_permute: NULL"); return -EINVAL; }
   return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {

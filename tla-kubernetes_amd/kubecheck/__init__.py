@@ -874,6 +874,14 @@ class Spec:
         check("kc_spec_fingerprint", self._lib.kc_spec_fingerprint(C.byref(self._c), _u64(t), C.byref(fp)))
         return fp.value
 
+    def fingerprint_own(self, tup) -> int:
+        """The fingerprint of the sharded path: fingerprint() with the owner
+        projection in its top bits (kc_shard_owner reads the owner from it)."""
+        t = np.ascontiguousarray(tup, dtype=np.uint64)
+        fp = C.c_uint64()
+        check("kc_spec_fingerprint_own", self._lib.kc_spec_fingerprint_own(C.byref(self._c), _u64(t), C.byref(fp)))
+        return fp.value
+
     def fingerprint_sym(self, tup) -> int:
         """The fingerprint the engine stores under cfg.symmetry: the minimum
         of fingerprint() over the state's permutation orbit."""

@@ -261,6 +261,8 @@ SIGNATURES = [
                                     C.c_uint64, _U64P, C.c_uint64, _U64P]),
     ("kc_emit_selftest", C.c_int, [C.c_int, C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P,
                                    C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64]),
+    ("kc_claim_selftest", C.c_int, [C.c_int, C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P,
+                                    C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64]),
     ("kc_probe_selftest", C.c_int, [C.c_int, C.c_uint64, _U64P, _U64P, C.c_uint64, C.c_uint32, C.c_int, _U64P,
                            _U64P, _U64P]),
     ("kc_sim_create", C.c_int, [C.POINTER(KcModelConfig), C.POINTER(KcSimConfig), C.POINTER(_P)]),
@@ -291,6 +293,7 @@ SIGNATURES = [
     ("kc_cover_count", C.c_int, []),
     ("kc_cover_name", C.c_char_p, [C.c_int]),
     ("kc_spec_fingerprint", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
+    ("kc_spec_fingerprint_own", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
     ("kc_spec_fp_selfcheck", C.c_int, [C.POINTER(KcModelConfig), _U64P]),
     ("kc_spec_permute", C.c_int, [C.POINTER(KcModelConfig), _U64P, _IP, _U64P]),
     ("kc_spec_fingerprint_sym", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
