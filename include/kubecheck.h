@@ -264,6 +264,32 @@ typedef struct {
    * with -EINVAL (the owner projection is not orbit-invariant; liveness under
    * symmetry is unsound), and so does kc_sim_create. */
   int symmetry;
+  /* Constraints (TLC's CONSTRAINT and ACTION_CONSTRAINT; DESIGN.md section
+   * 4.11).  A successor x of an expanded state s is in the model iff every
+   * state constraint holds in x and every action constraint holds on the step
+   * s -> x (state constraints first).  A successor outside the model still
+   * counts as generated; it is discarded without a seen-set lookup (not
+   * distinct, not queued, no trace link), after its invariants were checked.
+   * Deadlock is a property of Next alone; Init states outside a state
+   * constraint are discarded.  The vocabulary is build-defined:
+   *   constraint_stored   = k >= 0: StoredAtMost<k>, Cardinality(apiState) <= k
+   *   constraint_inflight = k >= 0: InFlightAtMost<k>, Cardinality(PendingClients)
+   *                         + Cardinality(PendingListClients) <= k
+   *   action_constraints  bit 0: ServeClientsFirst, an APIStart step that takes
+   *                         a PVC controller's request or list request out of
+   *                         "Pending" only while no client's is pending
+   * Negative bounds (kc_model_config_default sets -1) and mask 0 = off: then
+   * nothing changes and the plain engine runs.  Single-GPU in-HBM BFS only:
+   * kc_engine_create fails with -EINVAL together with symmetry,
+   * seen_hbm_bytes, frontier_hbm_bytes or trace_host, with mask bits outside
+   * bit 0, and for a model not built with constraints (built: (1,1,1),
+   * (2,1,1), (1,2,1), (1,3,1)); kc_engine_set_coverage, kc_engine_checkpoint,
+   * kc_engine_set_checkpoint and kc_engine_recover fail with -EINVAL on such
+   * an engine; kc_shard_create (so every kc_group_*), kc_live_create and
+   * kc_sim_create fail with -EINVAL. */
+  int constraint_stored;
+  int constraint_inflight;
+  int action_constraints;
 } kc_model_config;
 
 typedef struct {
@@ -327,6 +353,11 @@ typedef struct {
    * (rank, parent) order on shards), 1 = first inserter (cfg.first_claim),
    * 2 = TLC order on shards (cfg.tlc_order at world > 1) */
   int claim_mode;
+  /* constraints: successors (and Init states) discarded by a state
+   * constraint, and successors that passed those and were discarded by an
+   * action constraint; both 0 without constraints */
+  uint64_t cut_state;
+  uint64_t cut_action;
 } kc_result;
 
 typedef struct kc_engine kc_engine;
@@ -1021,6 +1052,26 @@ int kc_spec_fingerprint_sym(const kc_model_config *cfg, const uint64_t *tuple, u
 int kc_sym_selftest_fps(const kc_model_config *cfg, const uint64_t *tuples, uint64_t n, uint64_t *fps_out);
 int kc_spec_pack(const kc_model_config *cfg, const uint64_t *tuple, uint64_t *packed_out);
 int kc_spec_unpack(const kc_model_config *cfg, const uint64_t *packed, uint64_t *tuple_out);
+/* Constraints (cfg->constraint_stored, constraint_inflight,
+ * action_constraints), the host definition on canonical tuples: is successor
+ * tuple_x of tuple_s, made by action id `action`, in the model?  0 = in,
+ * 1 = cut by a state constraint, 2 = passed those and cut by an action
+ * constraint.  tuple_s may be NULL when no action constraint is set (an Init
+ * state); -EINVAL (< 0) when it is NULL while one is set, for a bad tuple,
+ * an action id outside the action table or a model not built with
+ * constraints. */
+int kc_spec_in_model(const kc_model_config *cfg, const uint64_t *tuple_s, const uint64_t *tuple_x, int action);
+/* Device harness (csrc/con_selftest.hip): the device code of the same hook
+ * over n (parent, successor, action) triples, one lane per pair; out[i] as
+ * kc_spec_in_model returns it.  -ENODEV without a GPU. */
+int kc_con_selftest(const kc_model_config *cfg, const uint64_t *tuples_s, const uint64_t *tuples_x,
+                    const int *actions, uint64_t n, int *out);
+/* Diagnostic (tests use it to see that a config with the constraint fields
+ * off runs the plain engine): which model type a kc_engine was built from,
+ * 0 = the plain model, 1 = under symmetry reduction, 2 = under constraints.
+ * Not something to branch on: what an engine computes is defined by its
+ * config alone. */
+int kc_engine_instantiation(kc_engine *e);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,7 @@ class EngineBase {
   virtual int trace_tuple(int i, uint64_t* out) const = 0;
   virtual int64_t level_tuples(int level, uint64_t* out, uint64_t cap) = 0;
   virtual int state_words() const = 0;
+  virtual int instantiation() const = 0;
   virtual int tuple_words() const = 0;
   virtual int check_fps(uint64_t* min_gap, double* prob) = 0;
   void set_capture(int level) { capture_level_ = level; }
@@ -74,6 +75,9 @@ std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg);
 // the engine under symmetry reduction (engine_sym.hip); eff = a mask with a
 // non-trivial group (kubeapi_spec.h sym_effective); nullptr for other models
 std::unique_ptr<EngineBase> make_engine_sym(const kc_model_config& cfg, int eff);
+// the engine under constraints (engine_con.hip: EngineT<ConModel<..>>);
+// nullptr for a model outside KC_FOR_EACH_CON_MODEL
+std::unique_ptr<EngineBase> make_engine_con(const kc_model_config& cfg);
 const char* action_name(int a);
 // k_cover (cover.hip) over n packed states of cfg's plain Model on `stream`
 // (a hipStream_t): their coverage base counters added into d_sums[KC_COVER_N]

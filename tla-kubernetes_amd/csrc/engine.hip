@@ -38,10 +38,16 @@
 // are compiled from this same text as a second translation unit
 // (engine_sym.hip defines KC_ENGINE_SYM_TU and includes this file): there the
 // launch helpers below are that unit's own copies, and it defines
-// make_engine_sym instead of make_engine and the C-ABI.
+// make_engine_sym instead of make_engine and the C-ABI.  The constrained
+// instantiations (EngineT<ConModel<..>>, kc_model_config.constraint_*) are a
+// third unit in the same way (engine_con.hip, KC_ENGINE_CON_TU,
+// make_engine_con).
+#if defined(KC_ENGINE_SYM_TU) || defined(KC_ENGINE_CON_TU)
+#define KC_ENGINE_DERIVED_TU 1
+#endif
 namespace kc {
 
-#ifndef KC_ENGINE_SYM_TU
+#ifndef KC_ENGINE_DERIVED_TU
 namespace {
 
 const char* kActionNames[A_COUNT] = {
@@ -126,7 +132,7 @@ __global__ void k_level_reset(Counters* __restrict__ C) {
   }
 }
 
-#ifndef KC_ENGINE_SYM_TU
+#ifndef KC_ENGINE_DERIVED_TU
 const char* action_name(int a) { return (a >= 0 && a < A_COUNT) ? kActionNames[a] : "?"; }
 #endif
 
@@ -174,7 +180,7 @@ __global__ void k_adjacent_min_gap(const unsigned long long* __restrict__ s, uin
   if (i + 1 < n) atomicMin(out, s[i + 1] - s[i]);
 }
 
-#ifdef KC_ENGINE_SYM_TU
+#ifdef KC_ENGINE_DERIVED_TU
 }  // namespace
 #endif
 
@@ -233,6 +239,10 @@ class EngineT final : public EngineBase {
   ~EngineT() override { (void)hipSetDevice(cfg_.device); }   // (the members free themselves on it)
 
   int state_words() const override { return M::W; }
+  // which model type this engine was built from: 0 plain, 1 SymModel, 2 ConModel
+  int instantiation() const override {
+    return M::CONSTRAINED ? 2 : std::is_same<Model<M::NC, M::NP, M::NS>, M>::value ? 0 : 1;
+  }
   int tuple_words() const override { return M::TUPLE_WORDS; }
 
   int setup() override {
@@ -284,6 +294,10 @@ class EngineT final : public EngineBase {
   // level's sums go to the host at the level's own sync and count once the
   // level is closed (a level the deferred frontier redoes is dropped first).
   int set_coverage(bool on) override {
+    if (on && M::CONSTRAINED) {
+      set_error("kc_engine_set_coverage: not with constraints (coverage counts every successor's expressions)");
+      return -EINVAL;
+    }
     if (on && !std::is_same<Model<M::NC, M::NP, M::NS>, M>::value) {   // (a SymModel)
       set_error("kc_engine_set_coverage: not under symmetry reduction (the states explored stand for orbits)");
       return -EINVAL;
@@ -361,6 +375,7 @@ class EngineT final : public EngineBase {
   // the trace file.  Nothing here runs, and nothing is allocated, unless one
   // of the three calls below was made.
   const char* ckpt_refusal() const {
+    if (M::CONSTRAINED) return "not with constraints (a checkpoint header names none)";
     if (spill_ || queued_ || cfg_.trace_host) return "not with seen_hbm_bytes, frontier_hbm_bytes or trace_host";
     if (cover_on_) return "not with coverage on (a checkpoint holds no coverage sums)";
     if (ablate_) return "not with KC_ABLATE";
@@ -776,11 +791,17 @@ class EngineT final : public EngineBase {
   // (under symmetry the fingerprint is the orbit's: of the Init states of
   // one orbit the first is kept, the others count as generated only)
   // the Init states kept (one per fingerprint), their fingerprints and successor count
-  uint64_t init_list(std::vector<State>& init, std::vector<uint64_t>& fps) const {
+  // (an Init state outside a state constraint is discarded: generated, not
+  // distinct, counted in cut_state)
+  uint64_t init_list(std::vector<State>& init, std::vector<uint64_t>& fps, uint64_t* cut = nullptr) const {
     uint64_t cand = 0;
     for (int k = 0; k < M::num_init(); ++k) {
       State s0;
       M::init_state(k, s0, cfg_.variant);
+      if (M::init_in_model(s0, flags_) != CUT_NONE) {
+        if (cut) ++*cut;
+        continue;
+      }
       const uint64_t fp0 = M::fingerprint(s0);
       if (std::find(fps.begin(), fps.end(), fp0) != fps.end()) continue;
       init.push_back(s0);
@@ -792,8 +813,48 @@ class EngineT final : public EngineBase {
   int seed_init(kc_result* res, LevelCursor& c, std::vector<State>& init) {
     const int ni_all = M::num_init();
     std::vector<uint64_t> fps;
-    const uint64_t cand = init_list(init, fps);
+    init_cut_ = 0;
+    const uint64_t cand = init_list(init, fps, &init_cut_);
     const int ni = (int)init.size();
+    // under constraints: the invariants of every Init state, the discarded
+    // ones included (TLC checks a state it did not find in the seen-set, and
+    // one outside the model is never looked up); and a run all of whose Init
+    // states are outside the constraint has nothing to explore.  Only a
+    // violating DISCARDED Init state (the first violator in Init order) is
+    // reported here, with the kept Init states counted as the path below
+    // counts them; a violating Init state inside the model is that path's.
+    if constexpr (M::CONSTRAINED) {
+      int bad = -1, inv = -1;
+      State s0;
+      for (int k = 0; k < ni_all && bad < 0; ++k) {
+        M::init_state(k, s0, cfg_.variant);
+        inv = M::check(s0, flags_.inv_mask);
+        if (inv >= 0) bad = k;
+      }
+      if (bad >= 0 && M::init_in_model(s0, flags_) == CUT_NONE) bad = -1;   // (in the model: reported below)
+      if (bad >= 0 || ni == 0) {
+        KC_HIP_TRY(hipMemsetAsync(d_ctr_, 0, sizeof(Counters), st_));
+        KC_HIP_TRY(hipStreamSynchronize(st_));
+        res->init = res->generated = ni_all;
+        res->distinct = ni;
+        if (ni) {
+          res->level_width[0] = ni;
+          res->nlevels = 1;
+        }
+        init_states_ = init;
+        c = LevelCursor{};
+        c.n = 0;
+        if (bad >= 0) {
+          res->err_kind = E_INVARIANT;
+          res->err_invariant = inv;
+          res->err_level = 1;
+          trace_.push_back(s0);
+          res->trace_len = 1;
+        }
+        finish(res, 0);
+        return kRunDone;
+      }
+    }
     // the seen-set allocation is kept across runs (cleared each run), like a
     // TLC FPSet pre-sized with -fpmem; it grows by rehash when needed
     const uint64_t fp_slots = cfg_.fpset_slots ? cfg_.fpset_slots : (1ull << 20);
@@ -1487,6 +1548,8 @@ class EngineT final : public EngineBase {
     res->generated = res->init + gen;
     res->depth = res->nlevels;
     res->queue_left = left;
+    res->cut_state = h_ctr_->cut_state() + init_cut_;
+    res->cut_action = h_ctr_->cut_action();
     res->complete = (left == 0 && res->err_kind == 0 && !(cfg_.max_levels && res->nlevels >= cfg_.max_levels && left));
     const double d = (double)res->distinct, gg = (double)res->generated;
     res->collision_optimistic = d * (gg - d) / 18446744073709551616.0;
@@ -2158,6 +2221,7 @@ class EngineT final : public EngineBase {
   DeviceArray<unsigned long long> d_ntrace_;
 
   Flags flags_{};
+  uint64_t init_cut_ = 0;       // Init states discarded by a state constraint (ConModel)
   bool cover_on_ = false, cover_valid_ = false;
   DeviceArray<unsigned long long> d_cover_;      // the current level's sums
   PinnedArray<unsigned long long> h_cover_;
@@ -2268,8 +2332,20 @@ std::unique_ptr<EngineBase> make_engine_sym(const kc_model_config& cfg, int eff)
 #undef KC_MAKE
   return nullptr;
 }
+#elif defined(KC_ENGINE_CON_TU)
+std::unique_ptr<EngineBase> make_engine_con(const kc_model_config& cfg) {
+#define KC_MAKE(a, b, c)                                              \
+  if (cfg.nc == a && cfg.np == b && cfg.ns == c)                      \
+    return std::unique_ptr<EngineBase>(new EngineT<ConModel<a, b, c>>(cfg));
+  KC_FOR_EACH_CON_MODEL(KC_MAKE)
+#undef KC_MAKE
+  return nullptr;
+}
 #else
 std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg) {
+  // a constraint: the ConModel instantiations (engine_con.hip); with the
+  // three fields at their defaults the plain engine runs
+  if (con_active(cfg.constraint_stored, cfg.constraint_inflight, cfg.action_constraints)) return make_engine_con(cfg);
   // symmetry with a non-trivial group: the SymModel instantiations
   // (engine_sym.hip); a mask that selects no group runs the plain engine
   if (const int eff = sym_effective(cfg.nc, cfg.np, cfg.symmetry)) return make_engine_sym(cfg, eff);
@@ -2284,7 +2360,7 @@ std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg) {
 
 }  // namespace kc
 
-#ifndef KC_ENGINE_SYM_TU
+#ifndef KC_ENGINE_DERIVED_TU
 
 using namespace kc;
 
@@ -2302,6 +2378,7 @@ void kc_model_config_default(kc_model_config* c) {
   c->check_deadlock = 1;
   c->keep_trace = 1;
   c->invariants = 3;
+  c->constraint_stored = c->constraint_inflight = -1;
 }
 
 int kc_engine_create(const kc_model_config* cfg, kc_engine** out) {
@@ -2319,9 +2396,28 @@ int kc_engine_create(const kc_model_config* cfg, kc_engine** out) {
       return -EINVAL;
     }
   }
+  const bool con = con_active(cfg->constraint_stored, cfg->constraint_inflight, cfg->action_constraints);
+  if (con) {
+    // constraints: the in-HBM single-GPU BFS only
+    if (cfg->action_constraints & ~AC_ALL) {
+      set_error("kc_engine_create: action_constraints %d outside 0..%d (bit 0 ServeClientsFirst)",
+                cfg->action_constraints, AC_ALL);
+      return -EINVAL;
+    }
+    if (cfg->symmetry) {
+      set_error("kc_engine_create: constraints are not supported under symmetry (TLC needs a symmetric constraint; "
+                "ServeClientsFirst and the bounds under `clients` would each need an argument)");
+      return -EINVAL;
+    }
+    if (cfg->seen_hbm_bytes || cfg->frontier_hbm_bytes || cfg->trace_host) {
+      set_error("kc_engine_create: constraints are not supported with seen_hbm_bytes, frontier_hbm_bytes or trace_host");
+      return -EINVAL;
+    }
+  }
   auto impl = make_engine(*cfg);
   if (!impl) {
-    set_error("kc_engine_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);
+    set_error("kc_engine_create: unsupported model nc=%d np=%d ns=%d%s", cfg->nc, cfg->np, cfg->ns,
+              con ? " with constraints" : "");
     return -EINVAL;
   }
   KC_TRY(impl->setup());
@@ -2381,6 +2477,11 @@ int kc_engine_recover(kc_engine* e, const char* dir) {
   return e->impl->recover(dir);
 }
 
+int kc_engine_instantiation(kc_engine* e) {
+  if (!e) { set_error("kc_engine_instantiation: NULL"); return -EINVAL; }
+  return e->impl->instantiation();
+}
+
 int kc_engine_narrow_times(kc_engine* e, double* ms, uint64_t* launches, uint64_t* levels) {
   if (!e || !ms || !launches || !levels) { set_error("kc_engine_narrow_times: NULL"); return -EINVAL; }
   e->impl->narrow_times(ms, launches, levels);
@@ -2399,4 +2500,4 @@ int kc_engine_kernel_times(kc_engine* e, double* ms4, uint64_t* launches4) {
 }
 
 }  // extern "C"
-#endif  // KC_ENGINE_SYM_TU
+#endif  // KC_ENGINE_DERIVED_TU

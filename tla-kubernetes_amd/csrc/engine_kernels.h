@@ -48,8 +48,12 @@ struct CtrStripe {                  // 1 KiB
   // (and loop_sorted: the wave trips if each tile's parents were dealt to
   // its waves in order of successor count)
   unsigned long long loop_max, loop_sum, loop_sorted;
-  unsigned long long pad[128 - 2 * A_COUNT - 19 - OUTDEG_BINS];
+  // constraints (ConModel): successors discarded by a state
+  // constraint / (having passed those) by an action constraint
+  unsigned long long cut_state, cut_action;
+  unsigned long long pad[128 - 2 * A_COUNT - 21 - OUTDEG_BINS];
 };
+static_assert(sizeof(CtrStripe) == 1024, "one stripe = 1 KiB (checkpoints hold the stripes)");
 struct Counters {
   unsigned long long err_key;     // min error key of the level (~0 = none)
   unsigned long long chunk_base;  // next-frontier offset of the current chunk
@@ -84,6 +88,8 @@ struct Counters {
   unsigned long long loop_max() const { return sum1(&CtrStripe::loop_max); }
   unsigned long long loop_sum() const { return sum1(&CtrStripe::loop_sum); }
   unsigned long long loop_sorted() const { return sum1(&CtrStripe::loop_sorted); }
+  unsigned long long cut_state() const { return sum1(&CtrStripe::cut_state); }
+  unsigned long long cut_action() const { return sum1(&CtrStripe::cut_action); }
   unsigned long long old_dist(int b) const {
     unsigned long long t = 0;
     for (int k = 0; k < CTR_STRIPES; ++k) t += s[k].old_dist[b];
@@ -798,6 +804,7 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
   __shared__ uint32_t sh_proj[OWN ? CLAIM_TILE : 1];  // OWN = 1: each parent's owner projection (kubeapi_spec.h)
   __shared__ unsigned int sh_rc;
   __shared__ unsigned int sh_nrep;                // tile representatives
+  __shared__ unsigned int sh_cut[2];              // ConModel: successors cut by a state / an action constraint
   // SH only (dynamic LDS): remote representatives per parent, then their
   // counts per owner packed 4 owners x 8 bits per word (a parent has <= 32)
   extern __shared__ unsigned int sh_dyn[];
@@ -807,6 +814,7 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
     sh_rc = 0;
     sh_nrep = 0;
     sh_dcand = 0;
+    if constexpr (M::CONSTRAINED) sh_cut[0] = sh_cut[1] = 0;
   }
   // DEAL: each tile's parents are dealt to its waves in order of successor
   // count (below), staged through the LDS table, which is cleared after that
@@ -1022,6 +1030,20 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
       } else {
         M::apply(s, slot, j, f, x, who);
       }
+      // a successor outside the model keeps its position t
+      // and is discarded here: no fingerprint, no LDS entry, no claim.  Its
+      // invariants are checked now (no later level rebuilds it), with the
+      // key the emit gives a new state at (parent, t).
+      if constexpr (M::CONSTRAINED) {
+        if (const int cut = M::in_model(s, x, slot, f)) {
+          if (ABL == 0) {
+            atomicAdd(&sh_cut[cut - 1], 1u);
+            if (M::check(x, f.inv_mask) >= 0)
+              atomicMin(&C->err_key, ((base + tile0 + KC_LP) << 16) | ((uint64_t)t << 8) | E_INVARIANT);
+          }
+          continue;
+        }
+      }
       uint64_t fp;
       if (ABL == 4) {
         fp = 0;
@@ -1212,6 +1234,10 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
   if (threadIdx.x < A_COUNT) {
     const unsigned int v = act_sum<AS>(sh_act, threadIdx.x);
     if (v) atomicAdd(&stripe(C).act_gen[threadIdx.x], (unsigned long long)v);
+  }
+  if constexpr (M::CONSTRAINED) {
+    if (threadIdx.x < 2 && sh_cut[threadIdx.x])
+      atomicAdd(threadIdx.x ? &stripe(C).cut_action : &stripe(C).cut_state, (unsigned long long)sh_cut[threadIdx.x]);
   }
   if (dfr) {
     if (threadIdx.x < A_COUNT) {

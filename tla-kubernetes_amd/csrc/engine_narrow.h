@@ -118,6 +118,8 @@ struct NarrowCtl {
   unsigned long long err[2];
   unsigned int act_next[2][A_COUNT];       // level L's per-action successor counts, committed when L runs
   unsigned int lt_over[2];                 // level L's table overflowed: it cannot run narrow
+  unsigned int cut_next[2][2];             // ConModel: level L's successors cut by a state / an action constraint,
+                                           // committed when L runs (as act_next)
   unsigned long long wg_pub[NARROW_FWG];   // k_nfinish: pub_tag(epoch, level) | workgroup's new states
   uint64_t widths[KC_MAX_LEVELS];          // widths[L] = width of level L + 1
 };
@@ -238,7 +240,11 @@ k_nexpand(const typename M::State* __restrict__ bufA, const typename M::State* _
   if (!active) return;
   NTRACE_X(1);
   __shared__ unsigned int sh_act[A_COUNT];
+  __shared__ unsigned int sh_cut[2];               // ConModel: successors cut by a state / an action constraint
   if (threadIdx.x < A_COUNT) sh_act[threadIdx.x] = 0;
+  if constexpr (M::CONSTRAINED) {
+    if (threadIdx.x < 2) sh_cut[threadIdx.x] = 0;
+  }
   __syncthreads();
   NarrowLT* __restrict__ lt = sc->lt[lev % NARROW_NLT];
   if (i < n) {
@@ -264,6 +270,17 @@ k_nexpand(const typename M::State* __restrict__ bufA, const typename M::State* _
       M::locate(pl, t, slot, j);
       State x;
       M::apply(s, slot, j, f, x, who);
+      // a successor outside the model: no table entry (its
+      // hidx slot is never its own: k_nfinish compares the entry's key), its
+      // invariants checked here
+      if constexpr (M::CONSTRAINED) {
+        if (const int cut = M::in_model(s, x, slot, f)) {
+          atomicAdd(&sh_cut[cut - 1], 1u);
+          if (M::check(x, f.inv_mask) >= 0)
+            atomicMin(&ctl->err[lev & 1], (i << 16) | ((uint64_t)t << 8) | E_INVARIANT);
+          continue;
+        }
+      }
       const uint64_t fp[1] = {M::fingerprint_succ(s, fold, x, who)};
       const unsigned int key[1] = {(unsigned int)((i << 5) | (uint64_t)t)};
       // (the host admitted this level at <= 1/2 table load: a probe run this
@@ -278,8 +295,13 @@ k_nexpand(const typename M::State* __restrict__ bufA, const typename M::State* _
   NTRACE_X(3);
   if (threadIdx.x < A_COUNT && sh_act[threadIdx.x])
     atomicAdd(&stripe(C).act_gen[threadIdx.x], (unsigned long long)sh_act[threadIdx.x]);
+  if constexpr (M::CONSTRAINED) {
+    if (threadIdx.x < 2 && sh_cut[threadIdx.x])
+      atomicAdd(threadIdx.x ? &stripe(C).cut_action : &stripe(C).cut_state, (unsigned long long)sh_cut[threadIdx.x]);
+  }
 }
 
+template <bool CON>
 __device__ __forceinline__ void narrow_step(NarrowCtl* __restrict__ ctl, Counters* __restrict__ C, uint64_t total,
                                             unsigned long long cnext, uint32_t lev);
 
@@ -289,7 +311,10 @@ constexpr int NX_LDS = 256;
 template <class M>
 __device__ __forceinline__ bool lt_enter_succ(NarrowLT* __restrict__ lt, unsigned short* __restrict__ hx,
                                               const typename M::State& x, const typename M::Plan& px, int tx,
-                                              unsigned int o, Flags f) {
+                                              unsigned int o, Flags f, NarrowCtl* __restrict__ ctl, unsigned int qq,
+                                              unsigned int* sh_cutn) {
+  // (ctl, qq, sh_cutn: ConModel only — a cut successor's invariant error is
+  // level L + 1's, its count goes to the workgroup's LDS pair)
   bool ok = true;
   const uint64_t foldx = M::fp_fold(x);
   constexpr int NB = 8;
@@ -305,7 +330,16 @@ __device__ __forceinline__ bool lt_enter_succ(NarrowLT* __restrict__ lt, unsigne
         M::locate(px, t0 + q, sl, j);
         typename M::State y;
         M::apply(x, sl, j, f, y, who);
-        fpx[q] = M::fingerprint_succ(x, foldx, y, who);
+        int cut = CUT_NONE;
+        if constexpr (M::CONSTRAINED) {
+          cut = M::in_model(x, y, sl, f);
+          if (cut) {
+            atomicAdd(&sh_cutn[cut - 1], 1u);
+            if (M::check(y, f.inv_mask) >= 0)
+              atomicMin(&ctl->err[qq], ((uint64_t)o << 16) | ((uint64_t)(t0 + q) << 8) | E_INVARIANT);
+          }
+        }
+        if (!cut) fpx[q] = M::fingerprint_succ(x, foldx, y, who);
       }
     }
     uint64_t h[NB];
@@ -353,6 +387,10 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
   __shared__ unsigned long long sh_pc[NARROW_THREADS / NARROW_ESUB];
   __shared__ unsigned int sh_pm[NARROW_THREADS / NARROW_ESUB], sh_pincl[NARROW_THREADS / NARROW_ESUB];
   __shared__ unsigned long long sh_all;
+  __shared__ unsigned int sh_cutn[2];               // ConModel: level L + 1's cut successors (state / action)
+  if constexpr (M::CONSTRAINED) {
+    if (threadIdx.x < 2) sh_cutn[threadIdx.x] = 0;
+  }
   if (threadIdx.x == 0) sh_nx = 0;
   if (threadIdx.x < A_COUNT) sh_actn[threadIdx.x] = 0;
   if (threadIdx.x < A_COUNT) sh_dist[threadIdx.x] = 0;
@@ -380,6 +418,10 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
     const uint32_t succ_level = level + 1;
     constexpr int PT = 32 / NARROW_ESUB;            // successors per lane, at most
     unsigned int hs[PT];
+    // (ConModel: a discarded successor's hidx entry is stale or 0, never its
+    // own slot; the key comparison below rejects it, and any 16-bit value is
+    // a slot of the table)
+    static_assert(NARROW_LT == 65536, "every unsigned short in hidx indexes the level table");
 #pragma unroll
     for (int k = 0; k < PT; ++k) hs[k] = sub + k * NARROW_ESUB < tot ? hx[sub + k * NARROW_ESUB] : 0u;
     ulonglong2 e[PT];
@@ -547,7 +589,8 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
           sh_xf[xs] = M::fp_fold(x);
           sh_xo[xs] = (unsigned int)o;
           sh_xt[xs] = (unsigned int)tx;
-        } else if (!lt_enter_succ<M>(lt_next, sc->hidx[qq], x, px, tx, (unsigned int)o, f)) {   // LDS full: this lane
+        } else if (!lt_enter_succ<M>(lt_next, sc->hidx[qq], x, px, tx, (unsigned int)o, f, ctl, qq,
+                                     sh_cutn)) {   // LDS full: this lane
           atomicOr(&ctl->lt_over[qq], 1u);
         }
       }
@@ -610,7 +653,18 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
           M::locate(pxx, t, sl2, j2);
           State y;
           M::apply(xx, sl2, j2, f, y, who2);
-          fpx[q] = M::fingerprint_succ(xx, sh_xf[lo], y, who2);
+          int cut = CUT_NONE;
+          // a successor outside the model: no table entry;
+          // its invariant error and its count are level L + 1's
+          if constexpr (M::CONSTRAINED) {
+            cut = M::in_model(xx, y, sl2, f);
+            if (cut) {
+              atomicAdd(&sh_cutn[cut - 1], 1u);
+              if (M::check(y, f.inv_mask) >= 0)
+                atomicMin(&ctl->err[qq], ((uint64_t)sh_xo[lo] << 16) | ((uint64_t)t << 8) | E_INVARIANT);
+            }
+          }
+          if (!cut) fpx[q] = M::fingerprint_succ(xx, sh_xf[lo], y, who2);
           kx[q] = (sh_xo[lo] << 5) | (unsigned int)t;
         }
       }
@@ -639,6 +693,9 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
   if (threadIdx.x < OUTDEG_BINS && sh_deg[threadIdx.x])
     atomicAdd(&stripe(C).outdeg[threadIdx.x], (unsigned long long)sh_deg[threadIdx.x]);
   if (threadIdx.x < A_COUNT && sh_actn[threadIdx.x]) atomicAdd(&ctl->act_next[qq][threadIdx.x], sh_actn[threadIdx.x]);
+  if constexpr (M::CONSTRAINED) {
+    if (threadIdx.x < 2 && sh_cutn[threadIdx.x]) atomicAdd(&ctl->cut_next[qq][threadIdx.x], sh_cutn[threadIdx.x]);
+  }
   // The last workgroup to get here closes the level.  Its inputs are all
   // device-scope atomics: every wave waits for its own to complete (an
   // s_waitcnt on all counters; no L2 write-back needed), then one returning
@@ -657,14 +714,16 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
   __syncthreads();
   if (sh_last && wv == 0) {
     const unsigned long long all = sh_all;
-    narrow_step(ctl, C, (all >> 28) & ((1ull << 28) - 1), all & ((1ull << 28) - 1), lev);
+    narrow_step<M::CONSTRAINED>(ctl, C, (all >> 28) & ((1ull << 28) - 1), all & ((1ull << 28) - 1), lev);
     NTRACE_F(10);
   }
 }
 
 // Wave 0 of the last k_nfinish workgroup to finish: close level L (its
 // `total` new states with `cnext` successors) and decide about L + 1; lane
-// a commits (L + 1 runs narrow) or drops action a's pre-expansion count.
+// a commits (L + 1 runs narrow) or drops action a's pre-expansion count
+// (CON, ConModel: lanes 32 and 33 do the same for the two cut counts).
+template <bool CON>
 __device__ __forceinline__ void narrow_step(NarrowCtl* __restrict__ ctl, Counters* __restrict__ C, uint64_t total,
                                             unsigned long long cnext, uint32_t lev) {
   NarrowCtl& c = *ctl;
@@ -708,6 +767,15 @@ __device__ __forceinline__ void narrow_step(NarrowCtl* __restrict__ ctl, Counter
     if (v) {
       if (keep) atomicAdd(&C->s[0].act_gen[lane], (unsigned long long)v);
       c.act_next[qq][lane] = 0;
+    }
+  }
+  if constexpr (CON) {
+    if (lane == 32 || lane == 33) {
+      const unsigned int v = __hip_atomic_load(&c.cut_next[qq][lane - 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (v) {
+        if (keep) atomicAdd(lane == 32 ? &C->s[0].cut_state : &C->s[0].cut_action, (unsigned long long)v);
+        c.cut_next[qq][lane - 32] = 0;
+      }
     }
   }
 }

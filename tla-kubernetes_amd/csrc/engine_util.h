@@ -16,6 +16,9 @@ namespace kc {
 inline Flags flags_of(const kc_model_config& c) {
   Flags f{c.can_fail, c.can_timeout, c.variant};
   f.inv_mask = c.invariants & 7;
+  f.con_stored = c.constraint_stored;
+  f.con_inflight = c.constraint_inflight;
+  f.act_con = c.action_constraints;
   return f;
 }
 

@@ -103,7 +103,19 @@ struct Flags {
   int variant;
   int inv_mask = 3;  // invariants checked (MC.cfg INVARIANT): bit 0 TypeOK, bit 1 OnlyOneVersion,
                      // bit 2 NoLostUpdate (build-defined)
+  // constraints (TLC's CONSTRAINT / ACTION_CONSTRAINT; read
+  // by ConModel only): the bounds of StoredAtMost / InFlightAtMost (negative
+  // = off) and the action-constraint mask (AC_* bits)
+  int con_stored = -1;
+  int con_inflight = -1;
+  int act_con = 0;
 };
+// action constraints (Flags::act_con, kc_model_config.action_constraints)
+constexpr int AC_SERVE_CLIENTS_FIRST = 1;
+constexpr int AC_ALL = 1;
+// what Model::in_model answers for a successor: in the model, or cut by a
+// state constraint, or (having passed those) by an action constraint
+enum Cut : int { CUT_NONE = 0, CUT_STATE = 1, CUT_ACTION = 2 };
 constexpr uint64_t GHOST_LOST = 1ull << 63;   // lostUpdate (word 0; see above)
 
 KC_HD constexpr int ceil_log2(int x) { return x <= 1 ? 0 : 1 + ceil_log2((x + 1) / 2); }
@@ -696,6 +708,19 @@ struct Model {
     return -1;
   }
 
+  // ----------------------------------------------------------- constraints
+  // TLC's CONSTRAINT / ACTION_CONSTRAINT: is successor x
+  // of s, made by the action of `slot`, inside the model (a Cut)?  The plain
+  // model has no constraint and answers "in" as a compile-time constant; the
+  // kernels call the hook only `if constexpr (M::CONSTRAINED)`, so their
+  // plain instantiations hold no trace of it.  ConModel (below) answers from
+  // Flags.  Deadlock is a property of Next alone (plan().total), whatever is
+  // cut, so the parent phase needs no hook.
+  static constexpr bool CONSTRAINED = false;
+  KC_HD static constexpr int in_model(const State&, const State&, int, const Flags&) { return CUT_NONE; }
+  // the state constraints alone (Init states; action constraints do not apply to Init)
+  KC_HD static constexpr int init_in_model(const State&, const Flags&) { return CUT_NONE; }
+
   // --------------------------------------------------------- fingerprint
   // 64-bit fingerprint of the canonical packed words, normalised the way the
   // FPSet stores it: MSB clear (TLC's disk FPSets reserve it), never 0.
@@ -1132,6 +1157,63 @@ struct SymModel : Model<NC_, NP_, NS_> {
 // X(NC, NP, NS, MASK)
 #define KC_FOR_EACH_SYM_MODEL(X) \
   X(2, 1, 1, 1) X(1, 2, 1, 2) X(2, 0, 1, 1) X(1, 3, 1, 2) X(2, 2, 1, 1) X(2, 2, 1, 2) X(2, 2, 1, 3)
+// The model under constraints (kc_model_config.constraint_stored,
+// constraint_inflight, action_constraints): the same states,
+// actions, invariants and fingerprints; in_model answers from Flags, and
+// EngineT<ConModel<..>> is the engine's kernel text instantiated once more
+// with the hook's call sites live (engine_con.hip).  The vocabulary is
+// build-defined (no TLA+ expression evaluator exists here); the bounds are
+// run-time values:
+//   StoredAtMost<k>    Cardinality(apiState) <= k: a popcount of word 0
+//                      below the ghost bit;
+//   InFlightAtMost<k>  Cardinality(PendingClients) +
+//                      Cardinality(PendingListClients) <= k (KubeAPI.tla:441-442):
+//                      the present and status fields of every actor word,
+//                      through the compile-time-actor accessors;
+//   ServeClientsFirst  (action) an APIStart step that takes a PVC controller's
+//                      requests[p] or listRequests[p] out of "Pending" is
+//                      allowed only if no client is in PendingClients \cup
+//                      PendingListClients in the unprimed state.
+template <int NC_, int NP_, int NS_>
+struct ConModel : Model<NC_, NP_, NS_> {
+  using Base = Model<NC_, NP_, NS_>;
+  using State = typename Base::State;
+  static constexpr bool CONSTRAINED = true;
+  static constexpr int A = Base::A;
+  // bit a: requests[a] is pending; bit A + a: listRequests[a] is
+  KC_HD static unsigned pending(const State& x) {
+    unsigned m = 0;
+    static_for<A>([&](auto CI) {
+      constexpr int c = CI;
+      if (Base::template fld<c>(x, Base::F_RQP, 1) && Base::template fld<c>(x, Base::F_RQST, 2) == ST_Pending)
+        m |= 1u << c;
+      if (Base::template fld<c>(x, Base::F_LRP, 1) && Base::template fld<c>(x, Base::F_LRST, 2) == ST_Pending)
+        m |= 1u << (A + c);
+    });
+    return m;
+  }
+  KC_HD static int stored(const State& x) { return popc(x.w[0] & (Base::U < 64 ? ~GHOST_LOST : ~0ull)); }
+  KC_HD static int init_in_model(const State& x, const Flags& f) {
+    if (f.con_stored >= 0 && stored(x) > f.con_stored) return CUT_STATE;
+    if (f.con_inflight >= 0 && popc((uint64_t)pending(x)) > f.con_inflight) return CUT_STATE;
+    return CUT_NONE;
+  }
+  // state constraints first; action constraints only for a successor that passes them
+  KC_HD static int in_model(const State& s, const State& x, int slot, const Flags& f) {
+    if (init_in_model(x, f) != CUT_NONE) return CUT_STATE;
+    if ((f.act_con & AC_SERVE_CLIENTS_FIRST) && slot >= 2 * A) {      // an APIStart step
+      constexpr unsigned CL = ((1u << NC_) - 1u) | (((1u << NC_) - 1u) << A);   // the clients' bits
+      const unsigned ps = pending(s);
+      if ((ps & ~pending(x) & ~CL) && (ps & CL)) return CUT_ACTION;
+    }
+    return CUT_NONE;
+  }
+};
+// Models built with constraints: X(NC, NP, NS)
+#define KC_FOR_EACH_CON_MODEL(X) X(1, 1, 1) X(2, 1, 1) X(1, 2, 1) X(1, 3, 1)
+// kc_model_config's constraint fields call for the ConModel instantiation
+inline bool con_active(int stored, int inflight, int act_con) { return stored >= 0 || inflight >= 0 || act_con != 0; }
+
 // cfg.symmetry restricted to the process sets that have two members or more
 inline int sym_effective(int nc, int np, int symmetry) {
   return ((symmetry & 1) && nc >= 2 ? 1 : 0) | ((symmetry & 2) && np >= 2 ? 2 : 0);

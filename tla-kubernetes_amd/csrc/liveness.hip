@@ -1077,6 +1077,10 @@ int kc_live_create(const kc_model_config* cfg, const kc_live_config* live, kc_li
     set_error("kc_live_create: symmetry is not supported (liveness checking under symmetry reduction is unsound)");
     return -EINVAL;
   }
+  if (con_active(cfg->constraint_stored, cfg->constraint_inflight, cfg->action_constraints)) {
+    set_error("kc_live_create: constraints are not supported (the behaviour graph is built from Next alone)");
+    return -EINVAL;
+  }
   auto impl = make_live(*cfg);
   if (!impl) {
     set_error("kc_live_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);

@@ -2205,6 +2205,10 @@ int kc_shard_create(const kc_model_config* cfg, int rank, int world, kc_shard** 
               "orbit-invariant)");
     return -EINVAL;
   }
+  if (con_active(cfg->constraint_stored, cfg->constraint_inflight, cfg->action_constraints)) {
+    set_error("kc_shard_create: constraints are not supported in the sharded loop (single-GPU engine only)");
+    return -EINVAL;
+  }
   auto impl = make_shard(*cfg, rank, world);
   if (!impl) {
     set_error("kc_shard_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);

@@ -394,6 +394,10 @@ int kc_sim_create(const kc_model_config* cfg, const kc_sim_config* sim, kc_sim**
     set_error("kc_sim_create: symmetry is not supported (random walks keep no seen-set to reduce)");
     return -EINVAL;
   }
+  if (con_active(cfg->constraint_stored, cfg->constraint_inflight, cfg->action_constraints)) {
+    set_error("kc_sim_create: constraints are not supported (the walks step through Next alone)");
+    return -EINVAL;
+  }
   if (sim->num_walks < 1 || sim->num_walks > KC_SIM_MAX_WALKS) {
     set_error("kc_sim_create: num_walks %llu outside 1..2^30", (unsigned long long)sim->num_walks);
     return -EINVAL;

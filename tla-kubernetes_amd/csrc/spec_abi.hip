@@ -379,6 +379,37 @@ int kc_sim_replay(const kc_model_config* cfg, uint64_t seed, int depth, uint64_t
   });
 }
 
+// Constraints (kubeapi_spec.h ConModel::in_model) on canonical tuples.  The
+// hook tells an APIStart step by its slot; every other action's slot is
+// below 2A.
+int kc_spec_in_model(const kc_model_config* cfg, const uint64_t* tuple_s, const uint64_t* tuple_x, int action) {
+  if (!cfg || !tuple_x) { set_error("kc_spec_in_model: NULL"); return -EINVAL; }
+  if (action < 0 || action >= A_COUNT) { set_error("kc_spec_in_model: action %d outside 0..%d", action, A_COUNT - 1); return -EINVAL; }
+  if (cfg->action_constraints & ~AC_ALL) {
+    set_error("kc_spec_in_model: action_constraints %d outside 0..%d", cfg->action_constraints, AC_ALL);
+    return -EINVAL;
+  }
+  if (cfg->action_constraints && !tuple_s) {
+    set_error("kc_spec_in_model: an action constraint needs the unprimed state");
+    return -EINVAL;
+  }
+#define KC_CON(a, b, c)                                                                      \
+  if (cfg->nc == a && cfg->np == b && cfg->ns == c) {                                        \
+    using M = ConModel<a, b, c>;                                                             \
+    M::State s, x;                                                                           \
+    if (!M::from_tuple(tuple_x, x) || (tuple_s && !M::from_tuple(tuple_s, s))) {             \
+      set_error("kc_spec_in_model: tuple outside the lowered domain");                       \
+      return -EINVAL;                                                                        \
+    }                                                                                        \
+    const Flags f = flags_of(*cfg);                                                          \
+    return tuple_s ? M::in_model(s, x, action == A_APIStart ? 2 * M::A : 0, f) : M::init_in_model(x, f); \
+  }
+  KC_FOR_EACH_CON_MODEL(KC_CON)
+#undef KC_CON
+  set_error("kc_spec_in_model: model nc=%d np=%d ns=%d is not built with constraints", cfg->nc, cfg->np, cfg->ns);
+  return -EINVAL;
+}
+
 int kc_spec_unpack(const kc_model_config* cfg, const uint64_t* packed, uint64_t* tuple) {
   if (!cfg || !packed || !tuple) { set_error("kc_spec_unpack: NULL"); return -EINVAL; }
   return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {

@@ -27,11 +27,12 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from ._lib import (ACTIONS, CKPT_SECTIONS, ERR_KINDS, FAIRNESS, INVARIANTS, LIVE_KINDS, PROPERTIES, SIM_KINDS,
+from ._lib import (ACTION_CONSTRAINTS, ACTIONS, CKPT_SECTIONS, CUTS, ERR_KINDS, FAIRNESS, INSTANTIATIONS, INVARIANTS,
+                   LIVE_KINDS, PROPERTIES, SIM_KINDS,
                    KcCheckpointInfo, KcCheckpointOptions, KcLiveConfig,
                    KcLiveResult, KcModelConfig, KcResult, KcSimConfig,
                    KcSimResult, KcSqueueConfig, KcSqueueStats, KubecheckError,
@@ -97,6 +98,34 @@ class ModelConfig:
     # level_width and act_dist count orbits; frontier states and traces stay
     # real states.  The single-GPU engine only (include/kubecheck.h).
     symmetry: Union[int, str] = 0
+    # constraints (TLC's CONSTRAINT / ACTION_CONSTRAINT): a
+    # successor outside them is generated, then discarded (after its invariant
+    # check) without a seen-set lookup.  Build-defined vocabulary:
+    # StoredAtMost<k> = constraint_stored=k (Cardinality(apiState) <= k),
+    # InFlightAtMost<k> = constraint_inflight=k (pending requests + pending
+    # list requests <= k); -1 = off.  action_constraints: 0, a name of
+    # ACTION_CONSTRAINTS ("ServeClientsFirst"), a list of names, or the mask.
+    # The single-GPU in-HBM BFS only (include/kubecheck.h).
+    constraint_stored: int = -1
+    constraint_inflight: int = -1
+    action_constraints: Union[int, str, Sequence[str]] = 0
+
+    @property
+    def action_constraints_mask(self) -> int:
+        a = self.action_constraints
+        if isinstance(a, str):
+            a = [a]
+        if isinstance(a, (list, tuple)):
+            m = 0
+            for name in a:
+                if name not in ACTION_CONSTRAINTS:
+                    raise ValueError(f"action constraint {name!r}: expected " + ", ".join(ACTION_CONSTRAINTS))
+                m |= ACTION_CONSTRAINTS[name]
+            return m
+        a = int(a or 0)
+        if a & ~sum(ACTION_CONSTRAINTS.values()):
+            raise ValueError(f"action_constraints {a}: the mask has bit 0 (ServeClientsFirst) only")
+        return a
 
     @property
     def symmetry_mask(self) -> int:
@@ -117,6 +146,9 @@ class ModelConfig:
                 continue
             if f[0] == "symmetry":
                 c.symmetry = self.symmetry_mask
+                continue
+            if f[0] == "action_constraints":
+                c.action_constraints = self.action_constraints_mask
                 continue
             setattr(c, f[0], int(getattr(self, f[0])))
         # the C string must outlive the engine's use of the config (copied at create)
@@ -164,6 +196,8 @@ class CheckResult:
     defer_redo_level: int = 0      # ... starting from this level (1 = Init; 0 = no redo)
     narrow_levels: int = 0         # levels run by the device-driven narrow kernel
     claim_mode: str = "minimum"    # the claims that ran: "minimum" (sequential-BFS / rank-major), "first", "tlc"
+    cut_state: int = 0             # constraints: successors (and Init states) discarded by a state constraint
+    cut_action: int = 0            # ... that passed those and were discarded by an action constraint
     trace: List[List[int]] = field(default_factory=list)
     trace_text: str = ""
     # expression-level coverage (run(coverage=True)): base counter name -> its
@@ -206,7 +240,8 @@ def _result(r: KcResult) -> CheckResult:
         cand_overflow_records=r.cand_overflow_records, cand_buffer_peak_bytes=r.cand_buffer_peak_bytes,
         deferred_states=r.deferred_states, defer_fallback=bool(r.defer_fallback),
         defer_redo_level=int(r.defer_redo_level), narrow_levels=int(r.narrow_levels),
-        claim_mode=CLAIM_MODES.get(r.claim_mode, str(r.claim_mode)))
+        claim_mode=CLAIM_MODES.get(r.claim_mode, str(r.claim_mode)),
+        cut_state=int(r.cut_state), cut_action=int(r.cut_action))
 
 
 @dataclass
@@ -269,6 +304,12 @@ class ModelChecker:
         self._coverage = False
         if coverage:
             self.set_coverage(True)
+
+    @property
+    def instantiation(self) -> str:
+        """The model type the engine was built from: "plain", "symmetry" or
+        "constraints" (a value of INSTANTIATIONS)."""
+        return INSTANTIATIONS[check("kc_engine_instantiation", self._lib.kc_engine_instantiation(self._h))]
 
     def set_coverage(self, on: bool) -> None:
         """Count expression-level coverage (TLC's -coverage) in the runs that
@@ -907,6 +948,32 @@ class Spec:
         t = np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, self.tuple_words)
         out = np.zeros(len(t), dtype=np.uint64)
         check("kc_sym_selftest_fps", self._lib.kc_sym_selftest_fps(C.byref(self._c), _u64(t), len(t), _u64(out)))
+        return out
+
+    def in_model(self, tup_s, tup_x, action) -> Optional[str]:
+        """Under cfg's constraints, is successor tup_x of tup_s (made by
+        `action`, a name of ACTIONS or its id) in the model?  None (in),
+        "state" or "action" (the kind of constraint that cuts it).  tup_s may
+        be None for an Init state when no action constraint is set (host; no GPU)."""
+        x = np.ascontiguousarray(tup_x, dtype=np.uint64)
+        s = None if tup_s is None else np.ascontiguousarray(tup_s, dtype=np.uint64)
+        a = ACTIONS.index(action) if isinstance(action, str) else int(action)
+        return CUTS[check("kc_spec_in_model", self._lib.kc_spec_in_model(
+            C.byref(self._c), None if s is None else _u64(s), _u64(x), a))]
+
+    def con_selftest(self, tuples_s, tuples_x, actions) -> np.ndarray:
+        """kc_spec_in_model's answer (0 in, 1 state-cut, 2 action-cut) for every
+        (parent, successor, action id) triple, computed on the GPU by the
+        device code the engine's kernels call (test harness)."""
+        s = np.ascontiguousarray(tuples_s, dtype=np.uint64).reshape(-1, self.tuple_words)
+        x = np.ascontiguousarray(tuples_x, dtype=np.uint64).reshape(-1, self.tuple_words)
+        a = np.ascontiguousarray(actions, dtype=np.int32)
+        if not (len(s) == len(x) == len(a)):
+            raise ValueError("con_selftest: parents, successors and actions differ in length")
+        out = np.zeros(len(a), dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        check("kc_con_selftest", self._lib.kc_con_selftest(C.byref(self._c), _u64(s), _u64(x), a.ctypes.data_as(ip),
+                                                           len(a), out.ctypes.data_as(ip)))
         return out
 
     def fp_selfcheck(self, tup) -> int:

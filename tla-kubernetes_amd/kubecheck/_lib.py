@@ -22,6 +22,13 @@ ACTIONS = [
     "PVCHavePVCs", "PVCDone", "APIStart",
 ]
 
+# action constraints (kc_model_config.action_constraints bits), and what
+# kc_spec_in_model / kc_con_selftest answer
+ACTION_CONSTRAINTS = {"ServeClientsFirst": 1}
+CUTS = {0: None, 1: "state", 2: "action"}
+# kc_engine_instantiation
+INSTANTIATIONS = {0: "plain", 1: "symmetry", 2: "constraints"}
+
 ERR_KINDS = {0: None, 1: "assertion", 2: "invariant", 3: "deadlock"}
 INVARIANTS = {0: "TypeOK", 1: "OnlyOneVersion", 2: "NoLostUpdate"}
 
@@ -39,6 +46,7 @@ class KcModelConfig(C.Structure):
         ("tlc_order", C.c_int),
         ("first_claim", C.c_int),
         ("symmetry", C.c_int),
+        ("constraint_stored", C.c_int), ("constraint_inflight", C.c_int), ("action_constraints", C.c_int),
     ]
 
 
@@ -65,6 +73,7 @@ class KcResult(C.Structure):
         ("deferred_states", C.c_uint64), ("defer_fallback", C.c_uint64),
         ("defer_redo_level", C.c_uint64), ("narrow_levels", C.c_uint64),
         ("claim_mode", C.c_int),
+        ("cut_state", C.c_uint64), ("cut_action", C.c_uint64),
     ]
 
 
@@ -298,6 +307,9 @@ SIGNATURES = [
     ("kc_spec_permute", C.c_int, [C.POINTER(KcModelConfig), _U64P, _IP, _U64P]),
     ("kc_spec_fingerprint_sym", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
     ("kc_sym_selftest_fps", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P]),
+    ("kc_spec_in_model", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P, C.c_int]),
+    ("kc_con_selftest", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P, _IP, C.c_uint64, _IP]),
+    ("kc_engine_instantiation", C.c_int, [_P]),
     ("kc_spec_pack", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
     ("kc_spec_unpack", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
 ]

@@ -61,6 +61,15 @@ counts are orbit counts.  SYMMETRY together with a PROPERTY list or with
 -simulate is an error (liveness under symmetry is unsound, as TLC warns; a
 random walk has no seen-set to reduce).  Without the keyword nothing changes.
 
+Constraints: `CONSTRAINT name ...` and `ACTION_CONSTRAINT name ...` in the cfg
+(models/Constraint.cfg) are TLC's: a successor outside them is generated,
+its invariants are checked, and it is discarded without a seen-set lookup
+(DESIGN.md §4.11).  The names are build-defined, as the SYMMETRY sets are:
+`StoredAtMost<k>`, `InFlightAtMost<k>` (one bound per family) and
+`ServeClientsFirst`; several are conjoined.  The 2187 line names them with the
+two discard counts.  Together with -simulate, a PROPERTY list, SYMMETRY,
+-coverage or the checkpoint flags they are an error.
+
 Expression-level coverage: with `-coverage` (TLC's flag; its optional
 argument, the minutes between periodic reports, is accepted and ignored: only
 the final block is printed) the engine also counts, on the GPU and over every
@@ -114,6 +123,13 @@ BUILD_INVARIANTS = ("NoLostUpdate",)
 # build-defined symmetry sets (there is no Permutations(...) to evaluate):
 # the cfg's SYMMETRY name -> ModelConfig.symmetry
 SYMMETRY_NAMES = {"SymClients": "clients", "SymControllers": "controllers", "SymActors": "actors"}
+# build-defined constraints (there is no TLA+ expression evaluator): the cfg's
+# CONSTRAINT names StoredAtMost<k> (Cardinality(apiState) <= k) and
+# InFlightAtMost<k> (pending requests + pending list requests <= k), one bound
+# per family; the ACTION_CONSTRAINT names -> ModelConfig.action_constraints
+CONSTRAINT_FAMILIES = {"StoredAtMost": "constraint_stored", "InFlightAtMost": "constraint_inflight"}
+ACTION_CONSTRAINT_NAMES = ("ServeClientsFirst",)
+KNOWN_CONSTRAINTS = tuple(f + "<k>" for f in CONSTRAINT_FAMILIES) + ACTION_CONSTRAINT_NAMES
 KNOWN_CONSTANTS = ("REQUESTS_CAN_FAIL", "REQUESTS_CAN_TIMEOUT", "defaultInitValue")  # :4-6,374
 
 
@@ -139,10 +155,11 @@ def parse_cfg(cfg_text: str, defs: Optional[Dict[str, str]] = None) -> dict:
     defs = defs or {}
     toks = _strip_comments(cfg_text).split()
     out: dict = {"constants": {}, "specification": None, "invariants": [], "properties": [],
-                 "symmetry": None}
+                 "symmetry": None, "constraints": [], "action_constraints": []}
     i, section = 0, None
     keywords = {"CONSTANT", "CONSTANTS", "SPECIFICATION", "INVARIANT", "INVARIANTS",
-                "PROPERTY", "PROPERTIES", "INIT", "NEXT", "SYMMETRY"}
+                "PROPERTY", "PROPERTIES", "INIT", "NEXT", "SYMMETRY",
+                "CONSTRAINT", "CONSTRAINTS", "ACTION_CONSTRAINT", "ACTION_CONSTRAINTS"}
     while i < len(toks):
         t = toks[i]
         if t in keywords:
@@ -173,6 +190,20 @@ def parse_cfg(cfg_text: str, defs: Optional[Dict[str, str]] = None) -> dict:
                 raise CfgError(f"SYMMETRY {t}: expected one of {tuple(SYMMETRY_NAMES)} (build-defined; "
                                "Permutations(...) expressions are not evaluated)")
             out["symmetry"] = t
+        elif section in ("CONSTRAINT", "CONSTRAINTS"):
+            m = re.fullmatch(r"(StoredAtMost|InFlightAtMost)(\d+)", t)
+            if not m:
+                raise CfgError(f"CONSTRAINT {t}: expected one of {KNOWN_CONSTRAINTS[:2]} (build-defined; "
+                               f"TLA+ expressions are not evaluated; known names: {KNOWN_CONSTRAINTS})")
+            if any(c.startswith(m.group(1)) for c in out["constraints"]):
+                raise CfgError(f"CONSTRAINT {t}: a second {m.group(1)}<k> bound (one per family)")
+            out["constraints"].append(t)
+        elif section in ("ACTION_CONSTRAINT", "ACTION_CONSTRAINTS"):
+            if t not in ACTION_CONSTRAINT_NAMES:
+                raise CfgError(f"ACTION_CONSTRAINT {t}: expected one of {ACTION_CONSTRAINT_NAMES} (build-defined; "
+                               f"known names: {KNOWN_CONSTRAINTS})")
+            if t not in out["action_constraints"]:
+                out["action_constraints"].append(t)
         else:
             raise CfgError(f"unsupported cfg token {t!r}")
         i += 1
@@ -204,6 +235,21 @@ def model_from_cfg(cfg: dict) -> dict:
         (4 if "NoLostUpdate" in cfg["invariants"] else 0)
     if cfg.get("symmetry"):
         kw["symmetry"] = SYMMETRY_NAMES[cfg["symmetry"]]
+    for c in cfg.get("constraints") or []:
+        m = re.fullmatch(r"(StoredAtMost|InFlightAtMost)(\d+)", c)
+        if not m:
+            raise CfgError(f"CONSTRAINT {c}: known names: {KNOWN_CONSTRAINTS}")
+        if CONSTRAINT_FAMILIES[m.group(1)] in kw:
+            raise CfgError(f"CONSTRAINT {c}: a second {m.group(1)}<k> bound (one per family)")
+        kw[CONSTRAINT_FAMILIES[m.group(1)]] = int(m.group(2))
+    if cfg.get("action_constraints"):
+        bad = [x for x in cfg["action_constraints"] if x not in ACTION_CONSTRAINT_NAMES]
+        if bad:
+            raise CfgError(f"unknown ACTION_CONSTRAINT(s) {bad}; known names: {KNOWN_CONSTRAINTS}")
+        kw["action_constraints"] = list(cfg["action_constraints"])
+    if ("constraint_stored" in kw or "constraint_inflight" in kw or "action_constraints" in kw) and cfg.get("symmetry"):
+        raise CfgError(f"CONSTRAINT / ACTION_CONSTRAINT with SYMMETRY {cfg['symmetry']}: TLC needs a symmetric "
+                       "constraint, and these would each need an argument")
     return kw
 
 
@@ -215,6 +261,22 @@ def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, ch
     from ._lib import PROPERTIES
 
     props = list(cfg["properties"])
+    if cfg.get("constraints") or cfg.get("action_constraints"):
+        # constraints: the single-GPU BFS alone
+        names = " ".join(list(cfg.get("constraints") or []) + list(cfg.get("action_constraints") or []))
+        if simulate:
+            raise CfgError(f"CONSTRAINT / ACTION_CONSTRAINT ({names}) with -simulate: the walks step through Next alone")
+        if props:
+            raise CfgError(f"CONSTRAINT / ACTION_CONSTRAINT ({names}) with a PROPERTY list: liveness is checked on "
+                           "the unconstrained behaviour graph")
+        if cfg.get("symmetry"):
+            raise CfgError(f"CONSTRAINT / ACTION_CONSTRAINT ({names}) with SYMMETRY {cfg['symmetry']}: TLC needs a "
+                           "symmetric constraint, and these would each need an argument")
+        if coverage:
+            raise CfgError(f"CONSTRAINT / ACTION_CONSTRAINT ({names}) with -coverage: not counted under constraints")
+        if checkpointing:
+            raise CfgError(f"CONSTRAINT / ACTION_CONSTRAINT ({names}) with -checkpoint / -recover: a checkpoint "
+                           "names no constraint")
     if checkpointing and props:
         raise CfgError("-checkpoint / -recover with a PROPERTY list: a checkpoint holds the BFS's state, "
                        "not the liveness graph")
@@ -708,7 +770,7 @@ def tstamp(t: float) -> str:
 def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = None,
              engine: str = "", ngpus: int = 1, symmetry: Optional[str] = None,
              coverage: Optional[Dict[str, int]] = None, procs=(1, 1, 1), recovered=None,
-             checkpointed=None) -> List[tuple]:
+             checkpointed=None, constraints: Optional[List[str]] = None) -> List[tuple]:
     """TLC -tool messages (code, class, body) for one check's result, in the
     order of the reference run (MC.out:1-1108).  coverage (a
     CheckResult.coverage of a model with procs = (nc, np, ns)) adds the
@@ -722,7 +784,9 @@ def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = 
     add(2262, f"kubecheck (TLC-compatible counts) {engine}".rstrip())
     add(2187, f"Running breadth-first search Model-Checking with {ngpus} MI355X GPU(s) "
               f"(kubecheck ClaimSet FPSet, HBM StateQueue)."
-              + (f" Symmetry set: {symmetry}." if symmetry else ""))
+              + (f" Symmetry set: {symmetry}." if symmetry else "")
+              + (f" Constraints: {' '.join(constraints)} ({r.cut_state} generated states discarded by a state "
+                 f"constraint, {r.cut_action} by an action constraint)." if constraints else ""))
     add(2185, f"Starting... ({tstamp(t_start)})")
     if recovered is not None:
         add(2197, f"Starting recovery from checkpoint {recovered[0]}/")
@@ -957,7 +1021,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     try:
         kw, props = check_from_cfg(parsed, a.simulate, a.coverage, a.checkpointing)
     except CfgError as e:
-        if not a.checkpointing:
+        # (a refused combination with the checkpoint flags or with a cfg's
+        # constraints ends in an Error line; the older refusals raise, as they did)
+        if not (a.checkpointing or parsed["constraints"] or parsed["action_constraints"]):
             raise
         print(f"Error: {e}", file=sys.stderr)
         return 1
@@ -1002,7 +1068,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             checkpointed = (metadir.rstrip("/"), info, os.path.getmtime(ck_file))
     out = messages(r, t0, t1, prob, kubecheck.load().kc_build_info().decode(), kubecheck.device_count(),
                    parsed["symmetry"], coverage=r.coverage if a.coverage else None, procs=(a.nc, a.np, a.ns),
-                   recovered=recovered, checkpointed=checkpointed)
+                   recovered=recovered, checkpointed=checkpointed,
+                   constraints=(parsed["constraints"] + parsed["action_constraints"]) or None)
     if not props or r.error is not None:
         for code, cls, body in out:
             print(msg(code, body, cls, a.tool), flush=True)
