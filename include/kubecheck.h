@@ -971,6 +971,36 @@ int kc_claim_selftest(int kind, const kc_model_config *cfg, const uint64_t *par,
                       uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *table, uint64_t ntable, uint64_t *out,
                       uint64_t nout, uint64_t *res, uint64_t nres);
 
+/* ------------------------------------------ Liveness graph kernels (tests) */
+/* The graph part of the liveness checker (csrc/live_graph.h: the trim, the SCC
+ * decomposition, F and the closure to L, the lassos, and the host loops that
+ * drive them) on a graph of the caller's making (csrc/live_selftest.hip).  The
+ * harness builds the CSR rows, marks alive = stay and terminal with the code
+ * k_live_mark runs, and then makes the call kc_live_run makes after its build.
+ * The data rules are kc_emit_selftest's: u64 words, sections uploaded as given
+ * and copied back whole behind KC_EMIT_FORE guard elements and the caller's aft
+ * guards, every input checked on the host first (-EINVAL with or without a
+ * GPU, -ENODEV only for good input).
+ * par = [n (1 .. 2^22), P (1 .. 8), fairness (0 / 1), path_cap (0 = what
+ *   kc_live_create allocates: n * (P + 3) under fairness 1, n under fairness 0,
+ *   where a given one must be at least n), aft].
+ * deg[n] = out-degrees, summing to ne < 2^31; edges[ne] = targets (< n) in CSR
+ *   order, eproc[ne] = the process of each (< P); stay[n] = 0 / 1; parent[n],
+ *   level[n] = the discovery order: level[0] = 1, levels never fall along the
+ *   index, a level-1 state has parent ~0, any other state has parent[i] < i on
+ *   level[i] - 1 with an edge parent[i] -> i.
+ * out = alive (= L), terminal, enabled, comp, fair: KC_EMIT_FORE + n + aft
+ *   words each; then path: KC_EMIT_FORE + path_cap + aft words.  enabled, comp
+ *   and fair come back as given under fairness 0.
+ * res = [stay, stay_terminal, removed, trim rounds, sccs, fair_sccs,
+ *   fair_states, live, live_terminal, SCC-phase launches, violated, lasso kind,
+ *   prefix, loop, len, lasso_err << 32 | -(the driver's return code: 0, or EIO
+ *   when it found no counterexample; the sections are still copied back)].
+ * Test-only. */
+int kc_live_selftest(const uint64_t *par, uint64_t npar, const uint64_t *deg, const uint64_t *edges, uint64_t ne,
+                     const uint64_t *eproc, const uint64_t *stay, const uint64_t *parent, const uint64_t *level,
+                     uint64_t *out, uint64_t nout, uint64_t *res, uint64_t nres);
+
 /* ------------------------------------------------ Checkpoint streams (tests) */
 /* Device harness for the checkpoint streams (csrc/ckpt_selftest.hip) on a
  * table of exactly nslots slots; layout 0 = 16-B {fp, ~claim} slots, 1 = the

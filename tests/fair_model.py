@@ -15,6 +15,8 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
+import numpy as np
+
 import live_model
 from live_model import PER_PROC
 
@@ -28,6 +30,19 @@ def edge_process(m, s, action: str, t) -> int:
     moved = [a for a in range(A) if s[1 + PER_PROC * a] != t[1 + PER_PROC * a]]
     assert len(moved) == 1, (action, moved)          # unambiguous on every model used
     return moved[0]
+
+
+def edge_process_by_pc(tuples, src, dst, A: int):
+    """The process of every edge src[k] -> dst[k] from the two canonical tuples
+    alone (rows of `tuples`), with no action name: the one actor whose pc word
+    moved, or the single server (process A) when none did.  For graphs too
+    large to build from the oracle; tests/test_live_graphs_host.py holds it
+    against edge_process on every edge of the small models."""
+    pcs = np.asarray(tuples)[:, [1 + PER_PROC * a for a in range(A)]]
+    moved = pcs[np.asarray(src, dtype=np.int64)] != pcs[np.asarray(dst, dtype=np.int64)]
+    count = moved.sum(axis=1)
+    assert count.size == 0 or count.max() <= 1          # unambiguous
+    return np.where(count == 1, moved.argmax(axis=1), A)
 
 
 def edge_procs(m) -> List[List[int]]:
@@ -166,17 +181,17 @@ def procs_of(m) -> List[List[int]]:
     return _procs_cache[id(m)]
 
 
-def check_lasso(m, want: FairVerdict, idx: List[int], prefix_len: int, kind: str, loop_start: int) -> None:
-    """The counterexample, as state indices of m, is valid by the definition:
-    an Init state, steps of the graph, a shortest prefix to L, everything from
-    there on inside S (so inside L), then a terminal state, or a cycle inside
-    one fair SCC that has, for every process, a step of it or a state with it
-    disabled."""
-    procs = procs_of(m)
-    nproc = m.nc + m.np + m.ns
-    assert len(idx) >= prefix_len >= 1 and m.level[idx[0]] == 1
+def check_lasso_graph(succ: Sequence[Sequence[int]], procs: Sequence[Sequence[int]], nproc: int,
+                      level: Sequence[int], want: FairVerdict, idx: List[int], prefix_len: int, kind: str,
+                      loop_start: int) -> None:
+    """The counterexample, as state indices of the graph (succ, procs) with BFS
+    levels `level`, is valid by the definition: an Init state, steps of the
+    graph, a shortest prefix to L, everything from there on inside S (so inside
+    L), then a terminal state, or a cycle inside one fair SCC that has, for
+    every process, a step of it or a state with it disabled."""
+    assert len(idx) >= prefix_len >= 1 and level[idx[0]] == 1
     for a, b in zip(idx, idx[1:]):
-        assert b in m.succ[a] and a != b
+        assert b in succ[a] and a != b
     assert prefix_len == want.min_level
     assert all(i not in want.live for i in idx[:prefix_len - 1])
     assert all(i in want.stay and i in want.live for i in idx[prefix_len - 1:])
@@ -186,13 +201,119 @@ def check_lasso(m, want: FairVerdict, idx: List[int], prefix_len: int, kind: str
         return
     assert kind == "back-to-state" and prefix_len - 1 <= loop_start < len(idx)
     cycle = idx[loop_start:]
-    assert idx[loop_start] in m.succ[last] and idx[loop_start] != last
+    assert idx[loop_start] in succ[last] and idx[loop_start] != last
     k = want.scc_of[cycle[0]]
     assert all(want.scc_of.get(i) == k for i in cycle)        # one fair SCC
     wit = 0
     for a, b in zip(cycle, cycle[1:] + cycle[:1]):
         wit |= ~want.enabled[a] & ((1 << nproc) - 1)
-        for j, p in zip(m.succ[a], procs[a]):
+        for j, p in zip(succ[a], procs[a]):
             if j == b:
                 wit |= 1 << p
     assert wit == (1 << nproc) - 1, bin(wit)
+
+
+def check_lasso(m, want: FairVerdict, idx: List[int], prefix_len: int, kind: str, loop_start: int) -> None:
+    """check_lasso_graph on live_model.Model m (idx = state indices of m)."""
+    check_lasso_graph(m.succ, procs_of(m), m.nc + m.np + m.ns, m.level, want, idx, prefix_len, kind, loop_start)
+
+
+NONE = 0xffffffff
+
+
+@dataclass
+class Schedule:
+    trim_rounds: int              # trim launches, the last (empty) one included
+    launches: int                 # reset, push, pull and close launches
+    outer_rounds: int             # reset launches that left something open
+    comp: List[int]               # per state: its SCC's label (NONE outside the trimmed set)
+    fair: Set[int]
+    live: Set[int]
+
+
+def jacobi_schedule(succ: Sequence[Sequence[int]], procs: Sequence[Sequence[int]], nproc: int,
+                    S: Set[int]) -> Schedule:
+    """The product's whole launch schedule (include/kubecheck.h, "Liveness";
+    DESIGN.md 4.7) as synchronous rounds on numpy arrays: every launch is
+    judged on the values it started with.  The trim to its fixed point; then
+    per outer round a reset launch (an open state with no open successor other
+    than itself becomes an SCC of its own, every other open state takes its
+    index as its colour), push launches (the largest colour moves along the
+    edges between open states) until one raises nothing and pull launches (a
+    state whose colour is its index joins, and so does an open state with a
+    successor of its colour that has joined) until one adds nothing, until a
+    reset leaves nothing open; then F by the definition and close launches (a
+    state with a successor that reaches F reaches F) until one adds nothing.
+    Counts every launch that the product follows with a counter read."""
+    n = len(succ)
+    src = np.array([i for i in range(n) for _ in succ[i]], dtype=np.int64)
+    dst = np.array([j for i in range(n) for j in succ[i]], dtype=np.int64)
+    prc = np.array([p for i in range(n) for p in procs[i]], dtype=np.int64)
+    keep = src != dst                                     # edges s -> s are dropped
+    src, dst, prc = src[keep], dst[keep], prc[keep]
+    idx = np.arange(n, dtype=np.int64)
+    full = (1 << nproc) - 1
+
+    def any_edge(mask):                                   # per state: has an edge selected by mask
+        out = np.zeros(n, dtype=bool)
+        out[src[mask]] = True
+        return out
+
+    enabled = np.zeros(n, dtype=np.int64)
+    np.bitwise_or.at(enabled, src, 1 << prc)
+    terminal = enabled == 0
+    alive = np.zeros(n, dtype=bool)
+    alive[sorted(S)] = True
+    trim_rounds = 0
+    while True:
+        trim_rounds += 1
+        die = alive & ~terminal & ~any_edge(alive[src] & alive[dst])
+        if not die.any():
+            break
+        alive &= ~die
+    comp = np.full(n, NONE, dtype=np.int64)
+    color = np.zeros(n, dtype=np.int64)
+    launches = outer = 0
+    while True:
+        launches += 1                                     # reset
+        opn = alive & (comp == NONE)
+        still = opn & any_edge(opn[src] & opn[dst])
+        single = opn & ~still
+        comp[single] = idx[single]
+        color[still] = idx[still]
+        if not still.any():
+            break
+        outer += 1
+        opn = still
+        while True:                                       # push
+            launches += 1
+            m = opn[src] & opn[dst] & (color[dst] < color[src])
+            if not m.any():
+                break
+            new = color.copy()
+            np.maximum.at(new, dst[m], color[src[m]])
+            color = new
+        while True:                                       # pull
+            launches += 1
+            opn = alive & (comp == NONE)
+            join = opn & ((color == idx) | any_edge(opn[src] & alive[dst] & (comp[dst] == color[src])))
+            if not join.any():
+                break
+            comp[join] = color[join]
+    # accumulate and mark
+    size = np.bincount(comp[alive], minlength=n)
+    wit = np.zeros(n, dtype=np.int64)
+    np.bitwise_or.at(wit, comp[alive], ~enabled[alive] & full)
+    inside = alive[src] & alive[dst] & (comp[src] == comp[dst])
+    np.bitwise_or.at(wit, comp[src[inside]], 1 << prc[inside])
+    fair_scc = (size > 1) & (wit == full)
+    F = alive & (terminal | fair_scc[np.where(alive, comp, 0)])
+    reach = F.copy()
+    while True:                                           # close
+        launches += 1
+        add = alive & ~reach & any_edge(reach[dst])
+        if not add.any():
+            break
+        reach |= add
+    return Schedule(trim_rounds, launches, outer, [int(c) for c in comp], set(np.flatnonzero(F).tolist()),
+                    set(np.flatnonzero(reach).tolist()))

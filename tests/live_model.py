@@ -57,6 +57,28 @@ def eliminate(succ: List[List[int]], alive: Set[int]):
         alive -= dead
 
 
+def check_next_lasso(succ, level, S: Set[int], L: Set[int], idx: List[int], prefix_len: int, kind: str,
+                     loop_start: int) -> None:
+    """The counterexample under WF_vars(Next), as state indices of the graph
+    `succ` with BFS levels `level`, is valid: an Init state, steps of the graph,
+    a shortest prefix to L (the elimination's result for the stay set S),
+    everything from there on inside S and L, then a step back to a state of the
+    walk or a state with no successor other than itself."""
+    assert kind in ("back-to-state", "stuttering")
+    assert len(idx) >= prefix_len >= 1 and level[idx[0]] == 1
+    for a, b in zip(idx, idx[1:]):
+        assert b in succ[a] and a != b
+    assert prefix_len == min(level[i] for i in L)
+    assert all(i in S and i in L for i in idx[prefix_len - 1:])
+    assert all(i not in L for i in idx[:prefix_len - 1])
+    others = [j for j in succ[idx[-1]] if j != idx[-1]]
+    if kind == "back-to-state":
+        assert prefix_len - 1 <= loop_start < len(idx)
+        assert idx[loop_start] in others
+    else:
+        assert loop_start == -1 and not others
+
+
 @dataclass
 class Verdict:
     stay: Set[int]

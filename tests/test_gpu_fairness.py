@@ -14,6 +14,7 @@ import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import kubecheck
@@ -158,10 +159,11 @@ def test_cli_fairness_process(oracle):
     assert last and int(last.group(2)) == n + 1
     loop = int(last.group(4)) if last.group(4) else None
     assert loop is None or 1 <= loop <= n
-    # A valid lasso.  Model_1's graph is too large for the Python model, so the same check is run here and
-    # its counterexample (of the same shape as the printed one: its identity is the device's choice) is
-    # judged state by state: steps of Next, stay from the prefix's end on, and a cycle that has for every
-    # process a step of it or a state with it disabled, which also puts it inside one fair SCC.
+    # A valid lasso.  The same check is run here and its counterexample (of the same shape as the printed
+    # one: its identity is the device's choice) is judged state by state with the host Spec: steps of Next,
+    # stay from the prefix's end on, and a cycle that has for every process a step of it or a state with it
+    # disabled, which also puts it inside one fair SCC.  (test_model1_exact below compares S, the SCC
+    # counts, F and the exact L of Model_1 with the host models.)
     sp = kubecheck.Spec(ModelConfig())
     with LivenessChecker(ModelConfig(), "ReconcileCompletes", fairness="process") as lc:
         r = lc.run()
@@ -194,3 +196,81 @@ def test_cli_fairness_process(oracle):
                     wit |= 1 << p
             wit |= ~enabled & 7
         assert wit == 7, bin(wit)                 # Model_1 has 3 processes
+
+
+# ---- Model_1, exact: the device's exported graph through the host models
+#
+# (property, |S|, SCCs of more than one state, fair SCCs, |F|, |L|, terminal in L, |L| under WF_vars(Next),
+#  terminal in S, min level of L); computed with fair_check and eliminate on the CPU, recomputed below
+MODEL1_TABLE = [
+    ("ReconcileCompletes", 150856, 998, 104, 140905, 149316, 0, 150856, 0, 1),
+    ("CleansUpProperly", 7442, 554, 56, 1832, 7442, 0, 7442, 0, 25),
+    ("ClientRestarts", 136237, 7135, 429, 3391, 83955, 0, 136237, 0, 2),
+    ("SomeActorRestarts", 115209, 0, 0, 0, 0, 0, 0, 0, None),
+]
+_model1 = {}
+
+
+def model1_run(pname):
+    """One fairness="process" run of the property on Model_1 and the host
+    models' answer on the graph it exported (cached per property)."""
+    if pname in _model1:
+        return _model1[pname]
+    prop = PROPERTIES.index(pname)
+    with LivenessChecker(ModelConfig(), pname, fairness="process") as lc:
+        r = lc.run()
+        tuples, alive = lc.alive()
+        src, dst, proc = lc.edge_procs()
+    n = len(tuples)
+    assert (n, len(src)) == (163408, 577734) and len(np.unique(tuples, axis=0)) == n
+    # S and the process of every edge, independently of the device's code
+    S = {i for i, t in enumerate(tuples.tolist()) if live_model.stay(prop, t, 1, 1)}
+    mine = fair_model.edge_process_by_pc(tuples, src, dst, 2)
+    assert (mine == proc).all()
+    succ, procs = [[] for _ in range(n)], [[] for _ in range(n)]   # (a state's edges keep their order)
+    for i, j, p in zip(src.tolist(), dst.tolist(), mine.tolist()):
+        succ[i].append(j)
+        procs[i].append(p)
+    # BFS levels: the Init states are the first indices, a level is a contiguous index range
+    level, todo = [0] * n, list(range(r.init))
+    for i in todo:
+        level[i] = 1
+    for i in todo:
+        for j in succ[i]:
+            if not level[j]:
+                level[j] = level[i] + 1
+                todo.append(j)
+    assert len(todo) == n and max(level) == 124 and level == sorted(level)
+    want = fair_model.fair_check(succ, procs, 3, S, level)
+    next_live, terminal, _ = live_model.eliminate(succ, S)
+    next_min = min((level[i] for i in next_live), default=None)
+    _model1[pname] = (r, tuples, alive, S, want, next_live, terminal, next_min)
+    return _model1[pname]
+
+
+@pytest.mark.parametrize("pname,n_stay,n_scc,n_fair_scc,n_fair,n_live,n_live_term,n_live_next,n_stay_term,min_level",
+                         MODEL1_TABLE, ids=[t[0] for t in MODEL1_TABLE])
+def test_model1_exact(pname, n_stay, n_scc, n_fair_scc, n_fair, n_live, n_live_term, n_live_next, n_stay_term,
+                      min_level):
+    r, tuples, alive, S, want, next_live, terminal, next_min = model1_run(pname)
+    # the literals against the models
+    assert (len(S), len(want.sccs), len(want.fair_sccs), len(want.fair)) == (n_stay, n_scc, n_fair_scc, n_fair)
+    assert (len(want.live), want.live_terminal, len(next_live), len(S & terminal)) == \
+        (n_live, n_live_term, n_live_next, n_stay_term)
+    assert want.live <= next_live
+    # per-process fairness: the counters and the exact L
+    assert r.error is None and (r.states, r.edges, r.depth) == (163408, 577734, 124)
+    assert (r.stay_states, r.sccs, r.fair_sccs, r.fair_states) == (n_stay, n_scc, n_fair_scc, n_fair)
+    assert (r.live_states, r.live_terminal, r.violated) == (n_live, n_live_term, n_fair > 0)
+    assert set(np.flatnonzero(alive).tolist()) == want.live
+    assert (r.prefix_len if r.violated else None) == want.min_level == min_level
+    # WF_vars(Next): a run of its own, whose discovery order need not be this one's; L as a set of states
+    with LivenessChecker(ModelConfig(), pname, fairness="next") as lc:
+        q = lc.run()
+        tuples_q, alive_q = lc.alive()
+    assert (q.states, q.edges, q.depth, q.stay_states) == (163408, 577734, 124, n_stay)
+    assert (q.live_states, q.live_terminal, q.violated) == (n_live_next, n_stay_term, n_live_next > 0)
+    assert (q.sccs, q.fair_sccs, q.fair_states) == (0, 0, 0)
+    key = lambda a: {row.tobytes() for row in a}
+    assert key(tuples_q[alive_q]) == key(tuples[sorted(next_live)])
+    assert (q.prefix_len if q.violated else None) == next_min

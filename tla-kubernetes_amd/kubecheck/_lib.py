@@ -293,6 +293,8 @@ SIGNATURES = [
     ("kc_live_stay", C.c_int, [C.POINTER(KcModelConfig), C.c_int, _U64P]),
     ("kc_live_edge_procs", C.c_int64, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _U8P, C.c_uint64]),
     ("kc_live_step_process", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_int]),
+    ("kc_live_selftest", C.c_int, [_U64P, C.c_uint64, _U64P, _U64P, C.c_uint64, _U64P, _U64P, _U64P, _U64P, _U64P,
+                                   C.c_uint64, _U64P, C.c_uint64]),
     ("kc_spec_tuple_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_state_words", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("kc_spec_init", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_int]),
