@@ -901,10 +901,19 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
         atomicMin(&C->err_key, (pidx << 16) | ((uint64_t)pl.fail_pos << 8) | E_ASSERT);
       else if (pl.total == 0 && check_deadlock)
         atomicMin(&C->err_key, (pidx << 16) | E_DEADLOCK);
+      // per-action "generated" (msg 2772), counted per actor: slots a and
+      // A + a are one actor's, and its pc enables at most one of them (a Do*
+      // label or a label of its own), so the two counts add up under the one
+      // action of that pc; the APIStart slots stand alone
+      static_for<M::A>([&](auto AI) {
+        constexpr int a = AI;
+        const int c = (int)((pl.counts >> (6 * a)) & 63) + (int)((pl.counts >> (6 * (M::A + a))) & 63);
+        if (c) atomicAdd(&sh_act[M::template slot_action_t<a>(s) * AS + (threadIdx.x & (AS - 1))], (unsigned)c);
+      });
 #pragma unroll
-      for (int slot = 0; slot < M::NSLOT; ++slot) {      // per-action "generated" (msg 2772)
+      for (int slot = 2 * M::A; slot < M::NSLOT; ++slot) {
         const int c = (int)((pl.counts >> (6 * slot)) & 63);
-        if (c) atomicAdd(&sh_act[M::slot_action(s, slot) * AS + (threadIdx.x & (AS - 1))], (unsigned)c);
+        if (c) atomicAdd(&sh_act[A_APIStart * AS + (threadIdx.x & (AS - 1))], (unsigned)c);
       }
     }
     tot = pl.total;

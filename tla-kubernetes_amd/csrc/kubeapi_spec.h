@@ -154,6 +154,47 @@ KC_HD void static_for(F&& f) {
   }
 }
 
+constexpr int PC_BITS = 5;   // the pc field of an actor word (Model::B_PC)
+// ---------------------------------------------------- label -> action
+// Action id of a label.  label_action_table is the map as a table;
+// label_action computes it: enum Label and enum Action list the client and
+// PVC labels (and APIStart after them) in the same order, and the four Do*
+// labels follow in both, so the map is two offsets and a range check (three
+// selects instead of a decision tree per use).  The static_asserts compare
+// the two for every value a pc field can hold: reordering either enum
+// fails the build.
+constexpr int label_action_table(int p) {
+  switch (p) {
+    case L_DoRequest: return A_DoRequest;   case L_DoReply: return A_DoReply;
+    case L_DoListRequest: return A_DoListRequest; case L_DoListReply: return A_DoListReply;
+    case L_CStart: return A_CStart; case L_C1: return A_C1; case L_C10: return A_C10;
+    case L_C11: return A_C11; case L_c12: return A_c12; case L_C13: return A_C13;
+    case L_C2: return A_C2; case L_C3: return A_C3; case L_C8: return A_C8;
+    case L_C6: return A_C6; case L_C7: return A_C7; case L_C4: return A_C4;
+    case L_C5: return A_C5; case L_PVCStart: return A_PVCStart;
+    case L_PVCListedPVCs: return A_PVCListedPVCs; case L_PVCHavePVCs: return A_PVCHavePVCs;
+    case L_PVCDone: return A_PVCDone;
+    default: return A_APIStart;
+  }
+}
+KC_HD constexpr int label_action(int p) {
+  int a = p + (A_CStart - L_CStart);                        // L_CStart .. L_APIStart
+  a = p >= L_DoRequest ? p - L_DoRequest : a;               // L_DoRequest .. L_DoListReply
+  return (unsigned)(p - L_CStart) > (unsigned)(L_DoListReply - L_CStart) ? (int)A_APIStart : a;
+}
+static_assert(L_APIStart - L_CStart == A_APIStart - A_CStart && L_DoRequest == L_APIStart + 1 &&
+                  L_DoListReply == L_COUNT - 1 && A_DoRequest == 0 && A_CStart == A_DoListReply + 1,
+              "label_action: enum Label and enum Action in the same order");
+constexpr bool label_action_ok() {
+  for (int p = 0; p < (1 << PC_BITS); ++p)
+    if (label_action(p) != label_action_table(p)) return false;
+  return true;
+}
+static_assert(label_action_ok(), "label_action differs from the label -> action table");
+
+// n << the 2-bit field of `label` (Model's packed per-label successor counts)
+constexpr uint64_t lbit2(int label, int n) { return (uint64_t)n << (2 * label); }
+
 template <int NC_, int NP_, int NS_>
 struct Model {
   static constexpr int NC = NC_, NP = NP_, NS = NS_;
@@ -171,7 +212,7 @@ struct Model {
   static constexpr int MAXSUCC = 32;            // successor slots per state
 
   // actor word field offsets (LSB first)
-  static constexpr int F_PC = 0, B_PC = 5;
+  static constexpr int F_PC = 0, B_PC = PC_BITS;
   static constexpr int F_RQP = F_PC + B_PC, F_RQST = F_RQP + 1, F_RQOP = F_RQST + 2,
                        F_RQOBJ = F_RQOP + 3;
   static constexpr int F_LRP = F_RQOBJ + OBJB, F_LRST = F_LRP + 1, F_LRK = F_LRST + 2;
@@ -335,37 +376,43 @@ struct Model {
   // action raises an Assert failure (C2 :598, C4 :639, APIStart :740).
   static constexpr int NSLOT = 2 * A + NS;
 
+  // The label switches below are lowered without control flow: a label is a
+  // per-lane value on the GPU, and a switch over it becomes a divergent
+  // decision tree there (no lookup tables for this target).  The labels
+  // whose own-label action has a fixed number of successors come from one
+  // packed constant, 2 bits per label; the value-dependent ones (C2 / C4 on
+  // the stored Secret, C6 and PVCHavePVCs by popcount, the two reply labels
+  // on their status) are selects on top of it.
+  static constexpr uint64_t CLIENT_FIXED =                             // CStart :529-531 has two
+      lbit2(L_CStart, 2) | lbit2(L_C1, 1) | lbit2(L_C10, 1) | lbit2(L_C11, 1) | lbit2(L_c12, 1) |
+      lbit2(L_C13, 1) | lbit2(L_C3, 1) | lbit2(L_C8, 1) | lbit2(L_C7, 1) | lbit2(L_C5, 1);
+  static constexpr uint64_t PVC_FIXED = lbit2(L_PVCStart, 1) | lbit2(L_PVCListedPVCs, 1) | lbit2(L_PVCDone, 1);
+  static_assert(2 * (1 << B_PC) <= 64, "2 bits per label in one word");
+
   template <int slot>
   KC_HD static int slot_count(const State& s, const Flags& f) {
     if constexpr (slot < A) {
       constexpr int a = slot;
       const int p = pc<a>(s);
-      const int nb = 1 + (f.can_fail ? 1 : 0) + (f.can_timeout ? 1 : 0);
-      if (p == L_DoRequest || p == L_DoListRequest) return nb;        // :472-480, :500-508
-      if (p == L_DoReply)                                              // :486-490
-        return fld<a>(s, F_RQST, 2) != ST_Pending ? 1 + (f.can_timeout ? 1 : 0) : 0;
-      if (p == L_DoListReply)                                          // :514-519
-        return fld<a>(s, F_LRST, 2) != ST_Pending ? 1 + (f.can_timeout ? 1 : 0) : 0;
-      return 0;
+      const int rep = 1 + (f.can_timeout ? 1 : 0);
+      const int nb = rep + (f.can_fail ? 1 : 0);
+      int c = (p == L_DoRequest || p == L_DoListRequest) ? nb : 0;     // :472-480, :500-508
+      c = p == L_DoReply ? (fld<a>(s, F_RQST, 2) != ST_Pending ? rep : 0) : c;       // :486-490
+      c = p == L_DoListReply ? (fld<a>(s, F_LRST, 2) != ST_Pending ? rep : 0) : c;   // :514-519
+      return c;
     } else if constexpr (slot < 2 * A) {
       constexpr int a = slot - A;
       const int p = pc<a>(s);
       if constexpr (is_client(a)) {
-        switch (p) {
-          case L_CStart: return 2;                                     // :529-531
-          case L_C1: case L_C10: case L_C11: case L_c12: case L_C13:
-          case L_C3: case L_C8: case L_C7: case L_C5: return 1;
-          case L_C2: return (s.w[0] & id_mask(ID_Secret)) ? 1 : -1;     // :598
-          case L_C4: return (s.w[0] & id_mask(ID_Secret)) ? -1 : 1;     // :639
-          case L_C6: return popc(objs<a>(s));                          // :619
-          default: return 0;
-        }
+        const bool secret = (s.w[0] & id_mask(ID_Secret)) != 0;
+        int c = (int)((CLIENT_FIXED >> (2 * p)) & 3);
+        c = p == L_C2 ? (secret ? 1 : -1) : c;                         // :598
+        c = p == L_C4 ? (secret ? -1 : 1) : c;                         // :639
+        c = p == L_C6 ? popc(objs<a>(s)) : c;                          // :619
+        return c;
       } else {
-        switch (p) {
-          case L_PVCStart: case L_PVCListedPVCs: case L_PVCDone: return 1;
-          case L_PVCHavePVCs: return popc(unbound(objs<a>(s)));        // :674
-          default: return 0;
-        }
+        const int c = (int)((PVC_FIXED >> (2 * p)) & 3);
+        return p == L_PVCHavePVCs ? popc(unbound(objs<a>(s))) : c;     // :674
       }
     } else {
       // APIStart (:698-756): one successor per pending request, then one per
@@ -397,26 +444,14 @@ struct Model {
       return A_APIStart;
     } else {
       constexpr int a = slot < A ? slot : slot - A;
-      switch (pc<a>(s)) {
-        case L_DoRequest: return A_DoRequest;   case L_DoReply: return A_DoReply;
-        case L_DoListRequest: return A_DoListRequest; case L_DoListReply: return A_DoListReply;
-        case L_CStart: return A_CStart; case L_C1: return A_C1; case L_C10: return A_C10;
-        case L_C11: return A_C11; case L_c12: return A_c12; case L_C13: return A_C13;
-        case L_C2: return A_C2; case L_C3: return A_C3; case L_C8: return A_C8;
-        case L_C6: return A_C6; case L_C7: return A_C7; case L_C4: return A_C4;
-        case L_C5: return A_C5; case L_PVCStart: return A_PVCStart;
-        case L_PVCListedPVCs: return A_PVCListedPVCs; case L_PVCHavePVCs: return A_PVCHavePVCs;
-        case L_PVCDone: return A_PVCDone;
-        default: return A_APIStart;
-      }
+      return label_action(pc<a>(s));
     }
   }
+  // ... of a run-time slot: the actor's word by selects (aw_d), its pc mapped
   KC_HD static int slot_action(const State& s, int slot) {
-    int r = A_APIStart;
-    static_for<NSLOT>([&](auto SI) {
-      if (slot == (int)SI) r = slot_action_t<SI>(s);
-    });
-    return r;
+    const int a = slot < A ? slot : slot - A;
+    const int act = label_action(g(aw_d(s, a), F_PC, B_PC));
+    return slot >= 2 * A ? (int)A_APIStart : act;
   }
 
   // Successor plan of a state: per-slot counts packed 6 bits each, the total
@@ -429,18 +464,18 @@ struct Model {
   };
   static_assert(NSLOT * 6 <= 64, "too many slots");
   KC_HD static Plan plan(const State& s, const Flags& f) {
+    // (every slot is evaluated, by selects: the slots after a failing one
+    // count nothing, and the first failure keeps its position)
     Plan pl{0, 0, -1, -1};
     static_for<NSLOT>([&](auto SI) {
       constexpr int slot = SI;
-      if (pl.fail_pos >= 0) return;
       const int c = slot_count<slot>(s, f);
-      if (c < 0) {
-        pl.fail_pos = pl.total;
-        pl.fail_slot = slot;
-        return;
-      }
-      pl.counts |= (uint64_t)(c > 63 ? 63 : c) << (6 * slot);
-      pl.total += c;
+      const bool first_fail = c < 0 && pl.fail_pos < 0;
+      pl.fail_pos = first_fail ? pl.total : pl.fail_pos;
+      pl.fail_slot = first_fail ? slot : pl.fail_slot;
+      const int cc = pl.fail_pos >= 0 ? 0 : c;
+      pl.counts |= (uint64_t)(cc > 63 ? 63 : cc) << (6 * slot);
+      pl.total += cc;
     });
     return pl;
   }
