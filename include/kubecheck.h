@@ -971,6 +971,94 @@ int kc_claim_selftest(int kind, const kc_model_config *cfg, const uint64_t *par,
                       uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *table, uint64_t ntable, uint64_t *out,
                       uint64_t nout, uint64_t *res, uint64_t nres);
 
+/* --------------------------- The sharded level's exchange kernels (tests) */
+/* The kernels of a sharded level (csrc/shard_kernels.h): the owner scans, the
+ * send buffer's gather and pack, the TLC-order renumbering, the deferred
+ * frontier's rebuild, the undo of a level's generated counts, and the insert
+ * of the received records with both emits, each on inputs of the caller's
+ * making, with the grids and block sizes ShardT launches them with
+ * (csrc/shard_selftest.hip).  The data rules are kc_emit_selftest's: u64 words,
+ * sections uploaded as given and copied back whole behind KC_EMIT_FORE guard
+ * elements and the caller's aft guards, every index checked on the host first
+ * (-EINVAL with or without a GPU, -ENODEV only for good input).  cfg is read by
+ * every kind but 0 and 2 (nc = ns = 1, np 1 or 2; variant, invariants and the
+ * constants apply).
+ * 0 the owner scans: par = [mode, world (1 to 15), T, status_new, status_err,
+ *   level1, init_err, want_row, aft]; mode 0 k_owner_tscan on tcnt[world][T],
+ *   1 k_owner_cscan on ocsum[world][T] (u32 cells, T >= 1, the scan's pad cells
+ *   hold 0xA5A5A5A5), 2 k_owner_scan_small and 3 hipcub's exclusive sum through
+ *   Widen8 + k_owner_totals on cnt[world][T] (u8 cells, T parents from 0; mode
+ *   2: world * T <= 16384).  a = the world * T cells, owner-major, summing below
+ *   2^32; b = the first ten words of Counters (err_key, chunk_base, overflow,
+ *   batch_used, cand_total, level_new, emit_done, defer_flags, defer_inv_n,
+ *   defer_err).  out = 5 sections: off (modes 0, 1: max(4 * ceil(cells / 4),
+ *   cells + 1) cells; 2, 3: cells), tot[16], host_tot[16] and host_head[10]
+ *   (pinned host memory), row[world + 3] (want_row 0: the kernel gets no row).
+ *   res = the world * T cells after the launch.
+ * 1 k_shard_gather<M>: par = [world, T (1 to 2^16 tiles), chunked, nstage,
+ *   aft]; a = the staging buffer, nstage records of raw words (4 at np 1, 6 at
+ *   np 2); b = stoff[T] (~0: nothing staged; else the tile's segment lies
+ *   inside the staging buffer), tcnt[world][T], then toff[world][T] (chunked 0)
+ *   or coff[world][ceil(T / 64)] (chunked 1): the owner-major exclusive sums of
+ *   tcnt, or of its 64-tile chunk sums.  out = one section: the send buffer,
+ *   exactly sum(tcnt) records.
+ * 2 TLC order: par = [nn, W (1 to 2^20), aft]; a = pkeys[nn] (parent G << 16 |
+ *   position << 8 | action), then link[nn]; b = other[W], the other ranks'
+ *   position words, OR-ed in after k_tlc_mask (the all-reduce's stand-in).
+ *   Then ShardT::tlc_order's sequence: the NewCount scan, k_tlc_pos, the bitmap
+ *   scan, k_tlc_perm.  out = 8 sections: wmask[W], wbase[W], gnew[nn],
+ *   bits[W + 1], brank[W + 1], link_out[nn], pk_out[nn], gpos_out[nn].  res =
+ *   [Counters::overflow].  With a key of G >= W or position >= 32 (counted as
+ *   overflow) only k_tlc_mask runs.
+ * 3 k_shard_pack<M>: par = [n, world, rank, with_gpos, aft]; a = n packed
+ *   parents raising no Assert; b = repmask[n] (bits below each parent's
+ *   successor count), then gpos[n] when with_gpos.  The harness gives the
+ *   kernel the owner-major exclusive sums of the marked successors per owner
+ *   and parent.  out = 2 sections: the send buffer (exactly the marked
+ *   successors' records), then the same records unpacked on the host (state
+ *   words, then the key).  res = the records per owner [world].
+ * 4 k_shard_materialize<M, tlc>: par = [n, nprev, nrec, rank, tlc, prev_counts,
+ *   aft]; a = nprev packed states raising no Assert, then (tlc 1)
+ *   prev_gpos[nprev]; b = link[n] (parent << 8 | position inside the previous
+ *   frontier and below the parent's successor count, or bit 63 | a record
+ *   index below nrec), then nrec records as state words + key (the harness
+ *   packs them).  out = n states.  res = [defer_err, next_cand, act_dist[22]].
+ * 5 k_undo_gen<M>: par = [n]; a = n packed states (an Assert parent is legal);
+ *   b = act_gen[22] before; the plans are Plan::counts of each state, what
+ *   k_claim keeps.  No out.  res = act_gen[22] after, mod 2^64.
+ * 6, 7 one rank's half of a level after the exchange, as ShardT::expand_dev,
+ *   insert and insert_emit launch it; 6 deterministic (k_head_reset, the
+ *   sharded k_claim, k_rec_claim, k_settle_both<M, 0>, k_settle_both<M, 1>, the
+ *   winners' scan, an emit), 7 first-claim (k_claim FIRST, k_rec_claim_first,
+ *   k_win_scan, an emit).
+ *   par = [n_local, nrec, level (the successors'), nslots, world (2 to 15),
+ *     rank, path, tlc, emit, cap, tail, unfused, next_gidx, aft, cap2, W].
+ *     path, kind 6: 0 = tile counts (pass B with wtot, then k_ovf_win_scan, or
+ *     with unfused 1 k_settle_ovf<1> + k_win_scan), 1 = pass B without wtot +
+ *     k_shard_scan_small, 2 = the same with hipcub's scans + k_shard_base; kind
+ *     7: 0 = 16-B slots, 1 = the compact table (nslots even).  tlc 1 (kind 6,
+ *     path 0, emit 1): TLC-order claim keys; a ends with gpos[n_local],
+ *     strictly increasing and below W, the level's width.  emit 0 =
+ *     k_shard_emit, 1 = k_shard_emit_links with cap (path 0 only); cap2 != 0:
+ *     after DF_CAPACITY the flags are cleared and the launch repeated with
+ *     cap2.  tail 1 = the emit runs the level tail, 0 = k_shard_cand.
+ *   a = n_local packed parents (0 is legal); b = nrec records as state words +
+ *     key, senders below world and not this rank (TLC: parent G below W).
+ *   table = the image, in and out, as kc_claim_selftest's; nslots >= stored +
+ *     the parents' successors + nrec + 1.
+ *   out = 11 sections: newmask[n_local], rfp[nrec], flag[nrec], isnew[nrec],
+ *     wtot and woff [own tiles + record blocks + 8] (path 0 and kind 7, else
+ *     empty), offsets[n_local] and ioff[nrec] (kind 6 path 1, 2, else empty),
+ *     next[bound states] (emit 0), link[bound] (emit 1), pkeys[next_gidx +
+ *     bound + 1]; bound = the parents' successors + nrec.
+ *   res = [err_key, overflow, probes, chunk_base, level_new, cand_total,
+ *     defer_flags, defer_flags after the first emit launch, act_dist[22], the
+ *     pinned host head's 10 words (0xA5.. before)].
+ * table is NULL for kinds 0 to 5.  Test-only. */
+int kc_shard_selftest(int kind, const kc_model_config *cfg, const uint64_t *par, uint64_t npar, const uint64_t *a,
+                      uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *table, uint64_t ntable, uint64_t *out,
+                      uint64_t nout, uint64_t *res, uint64_t nres);
+
 /* ------------------------------------------ Liveness graph kernels (tests) */
 /* The graph part of the liveness checker (csrc/live_graph.h: the trim, the SCC
  * decomposition, F and the closure to L, the lassos, and the host loops that

@@ -15,8 +15,11 @@ overflowing (kind 3: the lds_claim < 0 branch), chunk sums over 65 and 129
 tiles, the deferred rebuild, Assert / deadlock / invariant reports, record
 staging at world 2, 3, 4, 8 and a staging buffer that is too small.
 Not reached: the engine's own LDS-overflow branch (no state with 9 distinct
-successors exists in NP=3 levels 21 and 24, enumerated whole), TLC order, the
-sharded deferred rebuild, ocsum, a full seen-set (CL_FULL)."""
+successors exists in NP=3 levels 21 and 24, enumerated whole), ocsum as
+k_claim adds into it, the sharded deferred rebuild inside k_claim, a full
+seen-set (CL_FULL).  TLC-order claim keys, the received records' passes of
+k_settle_both, the rebuild through k_shard_materialize and k_owner_cscan on
+made chunk sums are test_gpu_shard_kernels.py's."""
 import numpy as np
 import pytest
 

@@ -34,6 +34,7 @@
 
 #include "../../include/kubecheck.h"
 #include "claim_launch.h"
+#include "claim_selftest_launch.h"
 #include "engine_kernels.h"
 #include "engine_util.h"
 #include "kc_common.h"
@@ -226,7 +227,6 @@ int run(int kind, const kc_model_config& cfg, const uint64_t* par, const uint64_
                    ovf_tile.as<unsigned int>(), ocap};
   if (first) sa.ttot = ttot.ptr();
   if (pf & PF_CSUM) sa.csum = csum.ptr();
-  size_t dyn = 0;
   if (sh) {
     sa.world = (uint32_t)world;
     sa.rank = (uint32_t)rank;
@@ -237,7 +237,6 @@ int run(int kind, const kc_model_config& cfg, const uint64_t* par, const uint64_
     sa.stage_cap = stage_cap;
     sa.tcnt = tcnt.ptr();
     sa.stoff = stoff.ptr();
-    dyn = (size_t)(CLAIM_TILE + ((world + 3) / 4) * CLAIM_TILE) * sizeof(unsigned int);
   }
   DeferArgs df;
   State* dout = reinterpret_cast<State*>(dfout.ptr());
@@ -262,8 +261,8 @@ int run(int kind, const kc_model_config& cfg, const uint64_t* par, const uint64_
     launch_claim<M, 0, false, 0, false, true, false>(nullptr, T, 0, dcur, n, base, f, dl, cs, lv, bufs, sa, df);
   else if (kind == 2)
     launch_claim<M, 0, false, 0, false, true, true>(nullptr, T, 0, dcur, n, base, f, dl, cs, lv, bufs, sa, df);
-  else
-    launch_claim<M, 0, true, 1>(nullptr, T, dyn, dcur, n, base, f, dl, cs, lv, bufs, sa, df);
+  else   // (base 0, no deferred frontier: checked above)
+    selftest::launch_shard_claim<M>(T, dcur, n, f, dl, cs, lv, bufs, sa);
   KC_HIP_TRY(hipGetLastError());
   if (!first) {
     // the engine's launch_settle (engine.hip), under the rank's claim keys

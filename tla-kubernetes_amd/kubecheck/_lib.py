@@ -272,6 +272,8 @@ SIGNATURES = [
                                    C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64]),
     ("kc_claim_selftest", C.c_int, [C.c_int, C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P,
                                     C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64]),
+    ("kc_shard_selftest", C.c_int, [C.c_int, C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P,
+                                    C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64, _U64P, C.c_uint64]),
     ("kc_probe_selftest", C.c_int, [C.c_int, C.c_uint64, _U64P, _U64P, C.c_uint64, C.c_uint32, C.c_int, _U64P,
                            _U64P, _U64P]),
     ("kc_sim_create", C.c_int, [C.POINTER(KcModelConfig), C.POINTER(KcSimConfig), C.POINTER(_P)]),
