@@ -290,6 +290,31 @@ typedef struct {
   int constraint_stored;
   int constraint_inflight;
   int action_constraints;
+  /* Action properties (TLC's PROPERTY with a formula [][A]_vars, a step
+   * invariant).  A is evaluated on every step
+   * s -> x the BFS generates, x new or seen, before the seen-set lookup; a
+   * step with x = s passes.  Init states are not steps.  The first level with
+   * a violating step ends the run: err_kind 4, err_invariant = the property's
+   * bit index, err_action / err_self = the step's, and the trace is the path
+   * to s followed by x (trace_len = depth(s) + 1).  Of the errors of one
+   * (parent, successor position) an invariant violation wins.  The level runs
+   * to its end, so step_checked and step_violations[] count whole levels.
+   * The vocabulary is build-defined:
+   *   bit 0 NoBlindUpdate: every requests[c] that is an Update, "Pending" in
+   *         s and "Ok" in x has a stored version of its object (unprimed
+   *         apiState) that c has read (HasRead)
+   *   bit 1 OneReplyPerStep: at most one requests[a] / listRequests[a] leaves
+   *         "Pending" in the step
+   *   bit 2 StoreNeverShrinks: Cardinality(apiState') >= Cardinality(apiState)
+   * Mask 0 = off: then nothing changes and the plain engine runs.
+   * Single-GPU in-HBM BFS only: kc_engine_create fails with -EINVAL together
+   * with constraints, symmetry, seen_hbm_bytes, frontier_hbm_bytes or
+   * trace_host, with mask bits outside 0..2, and for a model not built with
+   * action properties (built: (1,1,1), (2,1,1), (1,2,1), (1,3,1));
+   * kc_engine_set_coverage, kc_engine_checkpoint, kc_engine_set_checkpoint
+   * and kc_engine_recover fail with -EINVAL on such an engine; kc_shard_create
+   * (so every kc_group_*) and kc_sim_create fail with -EINVAL. */
+  int action_properties;
 } kc_model_config;
 
 typedef struct {
@@ -300,10 +325,11 @@ typedef struct {
   uint64_t act_dist[KC_NACTIONS];
   int nlevels;
   uint64_t level_width[KC_MAX_LEVELS];
-  int err_kind;            /* 0 none, 1 assertion, 2 invariant, 3 deadlock */
-  int err_action;          /* action id (assertion) */
+  int err_kind;            /* 0 none, 1 assertion, 2 invariant, 3 deadlock, 4 action property */
+  int err_action;          /* action id (assertion; the violating step of an action property) */
   int err_self;            /* process index of the failing action */
-  int err_invariant;       /* 0 TypeOK, 1 OnlyOneVersion */
+  int err_invariant;       /* 0 TypeOK, 1 OnlyOneVersion, 2 NoLostUpdate; err_kind 4: the action
+                            * property's bit index (0 NoBlindUpdate, 1 OneReplyPerStep, 2 StoreNeverShrinks) */
   int err_level;           /* BFS level of the last trace state */
   int trace_len;           /* states in the counterexample */
   double seconds;          /* wall time of the BFS (device work + host loop) */
@@ -358,6 +384,12 @@ typedef struct {
    * action constraint; both 0 without constraints */
   uint64_t cut_state;
   uint64_t cut_action;
+  /* action properties: the steps evaluated (every generated successor:
+   * generated - init) and the steps violating property k, summed over every
+   * level up to and including the one whose parents made the first
+   * violation; all 0 without action properties */
+  uint64_t step_checked;
+  uint64_t step_violations[3];
 } kc_result;
 
 typedef struct kc_engine kc_engine;
@@ -1186,10 +1218,23 @@ int kc_con_selftest(const kc_model_config *cfg, const uint64_t *tuples_s, const 
                     const int *actions, uint64_t n, int *out);
 /* Diagnostic (tests use it to see that a config with the constraint fields
  * off runs the plain engine): which model type a kc_engine was built from,
- * 0 = the plain model, 1 = under symmetry reduction, 2 = under constraints.
+ * 0 = the plain model, 1 = under symmetry reduction, 2 = under constraints,
+ * 3 = under action properties.
  * Not something to branch on: what an engine computes is defined by its
  * config alone. */
 int kc_engine_instantiation(kc_engine *e);
+/* Action properties (cfg->action_properties), the host definition on
+ * canonical tuples: the mask (>= 0) of the properties that the step
+ * tuple_s -> tuple_x, made by action id `action`, violates; 0 when the
+ * tuples are equal.  -EINVAL (< 0) for a bad tuple, an action id outside the
+ * action table, mask bits outside 0..2 or a model not built with action
+ * properties. */
+int kc_spec_step_violations(const kc_model_config *cfg, const uint64_t *tuple_s, const uint64_t *tuple_x, int action);
+/* Device harness (csrc/act_selftest.hip): the device code of the same hook
+ * over n (parent, successor, action) triples, one lane per pair; out[i] as
+ * kc_spec_step_violations returns it.  -ENODEV without a GPU. */
+int kc_act_selftest(const kc_model_config *cfg, const uint64_t *tuples_s, const uint64_t *tuples_x,
+                    const int *actions, uint64_t n, int *out);
 
 #ifdef __cplusplus
 }

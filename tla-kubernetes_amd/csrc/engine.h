@@ -78,6 +78,9 @@ std::unique_ptr<EngineBase> make_engine_sym(const kc_model_config& cfg, int eff)
 // the engine under constraints (engine_con.hip: EngineT<ConModel<..>>);
 // nullptr for a model outside KC_FOR_EACH_CON_MODEL
 std::unique_ptr<EngineBase> make_engine_con(const kc_model_config& cfg);
+// the engine under action properties (engine_act.hip: EngineT<ActModel<..>>);
+// nullptr for a model outside KC_FOR_EACH_ACT_MODEL
+std::unique_ptr<EngineBase> make_engine_act(const kc_model_config& cfg);
 const char* action_name(int a);
 // k_cover (cover.hip) over n packed states of cfg's plain Model on `stream`
 // (a hipStream_t): their coverage base counters added into d_sums[KC_COVER_N]

@@ -41,8 +41,10 @@
 // make_engine_sym instead of make_engine and the C-ABI.  The constrained
 // instantiations (EngineT<ConModel<..>>, kc_model_config.constraint_*) are a
 // third unit in the same way (engine_con.hip, KC_ENGINE_CON_TU,
-// make_engine_con).
-#if defined(KC_ENGINE_SYM_TU) || defined(KC_ENGINE_CON_TU)
+// make_engine_con), and the instantiations under action properties
+// (EngineT<ActModel<..>>, kc_model_config.action_properties) a fourth
+// (engine_act.hip, KC_ENGINE_ACT_TU, make_engine_act).
+#if defined(KC_ENGINE_SYM_TU) || defined(KC_ENGINE_CON_TU) || defined(KC_ENGINE_ACT_TU)
 #define KC_ENGINE_DERIVED_TU 1
 #endif
 namespace kc {
@@ -239,9 +241,9 @@ class EngineT final : public EngineBase {
   ~EngineT() override { (void)hipSetDevice(cfg_.device); }   // (the members free themselves on it)
 
   int state_words() const override { return M::W; }
-  // which model type this engine was built from: 0 plain, 1 SymModel, 2 ConModel
+  // which model type this engine was built from: 0 plain, 1 SymModel, 2 ConModel, 3 ActModel
   int instantiation() const override {
-    return M::CONSTRAINED ? 2 : std::is_same<Model<M::NC, M::NP, M::NS>, M>::value ? 0 : 1;
+    return M::STEP_CHECKED ? 3 : M::CONSTRAINED ? 2 : std::is_same<Model<M::NC, M::NP, M::NS>, M>::value ? 0 : 1;
   }
   int tuple_words() const override { return M::TUPLE_WORDS; }
 
@@ -296,6 +298,10 @@ class EngineT final : public EngineBase {
   int set_coverage(bool on) override {
     if (on && M::CONSTRAINED) {
       set_error("kc_engine_set_coverage: not with constraints (coverage counts every successor's expressions)");
+      return -EINVAL;
+    }
+    if (on && M::STEP_CHECKED) {
+      set_error("kc_engine_set_coverage: not with action properties (the coverage counters name none)");
       return -EINVAL;
     }
     if (on && !std::is_same<Model<M::NC, M::NP, M::NS>, M>::value) {   // (a SymModel)
@@ -376,6 +382,7 @@ class EngineT final : public EngineBase {
   // of the three calls below was made.
   const char* ckpt_refusal() const {
     if (M::CONSTRAINED) return "not with constraints (a checkpoint header names none)";
+    if (M::STEP_CHECKED) return "not with action properties (a checkpoint header names none)";
     if (spill_ || queued_ || cfg_.trace_host) return "not with seen_hbm_bytes, frontier_hbm_bytes or trace_host";
     if (cover_on_) return "not with coverage on (a checkpoint holds no coverage sums)";
     if (ablate_) return "not with KC_ABLATE";
@@ -1177,7 +1184,12 @@ class EngineT final : public EngineBase {
     // (first-claim mode: an Assert or deadlock key alone is reported below,
     // from the states this k_claim rebuilt into cur_, exactly as the
     // materialising path's k_claim of this level reports it — no redo)
-    const bool key_only = first_claim_ && !h.overflow && !h.batch_used && !h.defer_flags;
+    // (an action-property key is not reported from here: an invariant that a
+    // child of the same level violates may have the smaller key, and on the
+    // deferred frontier only the next level's rebuild would see it; the redo
+    // has both in one err_key)
+    const bool key_only = first_claim_ && !h.overflow && !h.batch_used && !h.defer_flags &&
+                          (h.err_key & 0xff) != E_ACTION_PROPERTY;
     if (dfr && !key_only && (h.overflow || h.batch_used || h.err_key != ~0ull || h.defer_flags)) {
       // an invariant violation among the states this level rebuilt is
       // the previous level's error (its emit would have found it); the
@@ -1474,6 +1486,23 @@ class EngineT final : public EngineBase {
       res->err_invariant = M::check(x, flags_.inv_mask);
       path.push_back(x);
       res->err_level = level + 1;
+    } else if (kind == E_ACTION_PROPERTY) {
+      // the step s -> x that violates the property: the behaviour is the
+      // path to s, then x (which may be a state seen levels ago)
+      int slot, j;
+      M::locate(pl, pos, slot, j);
+      State x;
+      M::apply(s, slot, j, flags_, x);
+      const unsigned bad = M::step_violations(s, x, slot, flags_);
+      if (!bad) {
+        set_error("kubecheck: the step of an action-property error key violates none");
+        return -EIO;
+      }
+      res->err_invariant = ctz(bad);
+      res->err_action = M::slot_action(s, slot);
+      res->err_self = slot < M::A ? slot : slot < 2 * M::A ? slot - M::A : M::A + (slot - 2 * M::A);
+      path.push_back(x);
+      res->err_level = level + 1;
     } else {
       res->err_level = level;
     }
@@ -1550,6 +1579,8 @@ class EngineT final : public EngineBase {
     res->queue_left = left;
     res->cut_state = h_ctr_->cut_state() + init_cut_;
     res->cut_action = h_ctr_->cut_action();
+    res->step_checked = h_ctr_->step_checked();
+    for (int k = 0; k < AP_COUNT; ++k) res->step_violations[k] = h_ctr_->step_violations(k);
     res->complete = (left == 0 && res->err_kind == 0 && !(cfg_.max_levels && res->nlevels >= cfg_.max_levels && left));
     const double d = (double)res->distinct, gg = (double)res->generated;
     res->collision_optimistic = d * (gg - d) / 18446744073709551616.0;
@@ -2341,8 +2372,21 @@ std::unique_ptr<EngineBase> make_engine_con(const kc_model_config& cfg) {
 #undef KC_MAKE
   return nullptr;
 }
+#elif defined(KC_ENGINE_ACT_TU)
+std::unique_ptr<EngineBase> make_engine_act(const kc_model_config& cfg) {
+#define KC_MAKE(a, b, c)                                              \
+  if (cfg.nc == a && cfg.np == b && cfg.ns == c)                      \
+    return std::unique_ptr<EngineBase>(new EngineT<ActModel<a, b, c>>(cfg));
+  KC_FOR_EACH_ACT_MODEL(KC_MAKE)
+#undef KC_MAKE
+  return nullptr;
+}
 #else
 std::unique_ptr<EngineBase> make_engine(const kc_model_config& cfg) {
+  // action properties: the ActModel instantiations (engine_act.hip); with
+  // the mask 0 the plain engine runs (kc_engine_create refused them together
+  // with constraints or symmetry)
+  if (cfg.action_properties) return make_engine_act(cfg);
   // a constraint: the ConModel instantiations (engine_con.hip); with the
   // three fields at their defaults the plain engine runs
   if (con_active(cfg.constraint_stored, cfg.constraint_inflight, cfg.action_constraints)) return make_engine_con(cfg);
@@ -2414,10 +2458,33 @@ int kc_engine_create(const kc_model_config* cfg, kc_engine** out) {
       return -EINVAL;
     }
   }
+  if (cfg->action_properties) {
+    // action properties: the in-HBM single-GPU BFS only
+    if (cfg->action_properties & ~AP_ALL) {
+      set_error("kc_engine_create: action_properties %d outside 0..%d (bit 0 NoBlindUpdate, bit 1 OneReplyPerStep, "
+                "bit 2 StoreNeverShrinks)", cfg->action_properties, AP_ALL);
+      return -EINVAL;
+    }
+    if (con) {
+      set_error("kc_engine_create: action properties are not supported with constraints (a step out of the model "
+                "would need TLC's rule for both)");
+      return -EINVAL;
+    }
+    if (cfg->symmetry) {
+      set_error("kc_engine_create: action properties are not supported under symmetry (a step is checked between "
+                "real states, the seen-set holds orbits)");
+      return -EINVAL;
+    }
+    if (cfg->seen_hbm_bytes || cfg->frontier_hbm_bytes || cfg->trace_host) {
+      set_error("kc_engine_create: action properties are not supported with seen_hbm_bytes, frontier_hbm_bytes or "
+                "trace_host");
+      return -EINVAL;
+    }
+  }
   auto impl = make_engine(*cfg);
   if (!impl) {
     set_error("kc_engine_create: unsupported model nc=%d np=%d ns=%d%s", cfg->nc, cfg->np, cfg->ns,
-              con ? " with constraints" : "");
+              con ? " with constraints" : cfg->action_properties ? " with action properties" : "");
     return -EINVAL;
   }
   KC_TRY(impl->setup());

@@ -51,7 +51,10 @@ struct CtrStripe {                  // 1 KiB
   // constraints (ConModel): successors discarded by a state
   // constraint / (having passed those) by an action constraint
   unsigned long long cut_state, cut_action;
-  unsigned long long pad[128 - 2 * A_COUNT - 21 - OUTDEG_BINS];
+  // action properties (ActModel): steps that violate
+  // property k, and the steps the hook evaluated (every generated successor)
+  unsigned long long step_violations[AP_COUNT], step_checked;
+  unsigned long long pad[128 - 2 * A_COUNT - 21 - AP_COUNT - 1 - OUTDEG_BINS];
 };
 static_assert(sizeof(CtrStripe) == 1024, "one stripe = 1 KiB (checkpoints hold the stripes)");
 struct Counters {
@@ -90,6 +93,12 @@ struct Counters {
   unsigned long long loop_sorted() const { return sum1(&CtrStripe::loop_sorted); }
   unsigned long long cut_state() const { return sum1(&CtrStripe::cut_state); }
   unsigned long long cut_action() const { return sum1(&CtrStripe::cut_action); }
+  unsigned long long step_checked() const { return sum1(&CtrStripe::step_checked); }
+  unsigned long long step_violations(int k) const {
+    unsigned long long t = 0;
+    for (int q = 0; q < CTR_STRIPES; ++q) t += s[q].step_violations[k];
+    return t;
+  }
   unsigned long long old_dist(int b) const {
     unsigned long long t = 0;
     for (int k = 0; k < CTR_STRIPES; ++k) t += s[k].old_dist[b];
@@ -805,6 +814,9 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
   __shared__ unsigned int sh_rc;
   __shared__ unsigned int sh_nrep;                // tile representatives
   __shared__ unsigned int sh_cut[2];              // ConModel: successors cut by a state / an action constraint
+  // ActModel: steps violating action property k; [AP_COUNT]: steps checked
+  constexpr bool STEPS = M::STEP_CHECKED && !SH && ABL == 0;
+  __shared__ unsigned int sh_step[AP_COUNT + 1];
   // SH only (dynamic LDS): remote representatives per parent, then their
   // counts per owner packed 4 owners x 8 bits per word (a parent has <= 32)
   extern __shared__ unsigned int sh_dyn[];
@@ -815,6 +827,9 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
     sh_nrep = 0;
     sh_dcand = 0;
     if constexpr (M::CONSTRAINED) sh_cut[0] = sh_cut[1] = 0;
+    if constexpr (STEPS) {
+      for (int k = 0; k <= AP_COUNT; ++k) sh_step[k] = 0;
+    }
   }
   // DEAL: each tile's parents are dealt to its waves in order of successor
   // count (below), staged through the LDS table, which is cleared after that
@@ -1019,6 +1034,9 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
     if (SWAR) counts = M::plan_cum(counts);
     const typename M::Plan pl{counts, tot, -1, -1};
     uint64_t acc = fold ^ counts;
+    if constexpr (STEPS) {
+      if (tot) atomicAdd(&sh_step[AP_COUNT], (unsigned)tot);   // (the loop below checks every one)
+    }
     // (walking (slot, j) along with t instead of locate() measured slower:
     // its three live registers spill at k_claim's 80-VGPR budget; r03w)
     for (int t = 0; t < tot; ++t) {
@@ -1038,6 +1056,18 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
           if (k == who) x.w[1 + k] ^= (uint64_t)(j + 1) << (slot & 31);
       } else {
         M::apply(s, slot, j, f, x, who);
+      }
+      // an action property is checked on every step, before
+      // the dedup: the child may have been claimed levels ago.  The key is
+      // the one an invariant violation of the child at (parent, t) gets, with
+      // a larger kind, so the invariant wins.
+      if constexpr (STEPS) {
+        if (const unsigned bad = M::step_violations(s, x, slot, f)) {
+          atomicMin(&C->err_key, ((base + tile0 + KC_LP) << 16) | ((uint64_t)t << 8) | E_ACTION_PROPERTY);
+#pragma unroll
+          for (int k = 0; k < AP_COUNT; ++k)
+            if ((bad >> k) & 1) atomicAdd(&sh_step[k], 1u);
+        }
       }
       // a successor outside the model keeps its position t
       // and is discarded here: no fingerprint, no LDS entry, no claim.  Its
@@ -1247,6 +1277,11 @@ k_claim(const typename M::State* __restrict__ cur, uint64_t n, uint64_t base, Fl
   if constexpr (M::CONSTRAINED) {
     if (threadIdx.x < 2 && sh_cut[threadIdx.x])
       atomicAdd(threadIdx.x ? &stripe(C).cut_action : &stripe(C).cut_state, (unsigned long long)sh_cut[threadIdx.x]);
+  }
+  if constexpr (STEPS) {
+    if (threadIdx.x <= AP_COUNT && sh_step[threadIdx.x])
+      atomicAdd(threadIdx.x < AP_COUNT ? &stripe(C).step_violations[threadIdx.x] : &stripe(C).step_checked,
+                (unsigned long long)sh_step[threadIdx.x]);
   }
   if (dfr) {
     if (threadIdx.x < A_COUNT) {

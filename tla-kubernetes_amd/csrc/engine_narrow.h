@@ -120,6 +120,8 @@ struct NarrowCtl {
   unsigned int lt_over[2];                 // level L's table overflowed: it cannot run narrow
   unsigned int cut_next[2][2];             // ConModel: level L's successors cut by a state / an action constraint,
                                            // committed when L runs (as act_next)
+  unsigned int step_next[2][AP_COUNT + 1]; // ActModel: level L's steps violating action property k and
+                                           // ([AP_COUNT]) its steps checked, committed when L runs
   unsigned long long wg_pub[NARROW_FWG];   // k_nfinish: pub_tag(epoch, level) | workgroup's new states
   uint64_t widths[KC_MAX_LEVELS];          // widths[L] = width of level L + 1
 };
@@ -218,6 +220,23 @@ __device__ __forceinline__ bool lt_enter(NarrowLT* __restrict__ lt, const uint64
   return ok;
 }
 
+// The action-property hook of the narrow kernels (ActModel):
+// the step s -> x, successor t of parent `o` of its level, is counted as
+// checked and, where it violates a property, gives the level's error word
+// the key k_claim gives it; sh_step = the workgroup's AP_COUNT + 1 sums.
+template <class M>
+__device__ __forceinline__ void step_check(const typename M::State& s, const typename M::State& x, int slot,
+                                           const Flags& f, unsigned long long* err, uint64_t o, int t,
+                                           unsigned int* sh_step) {
+  atomicAdd(&sh_step[AP_COUNT], 1u);
+  if (const unsigned bad = M::step_violations(s, x, slot, f)) {
+    atomicMin(err, (o << 16) | ((uint64_t)t << 8) | E_ACTION_PROPERTY);
+#pragma unroll
+    for (int k = 0; k < AP_COUNT; ++k)
+      if ((bad >> k) & 1) atomicAdd(&sh_step[k], 1u);
+  }
+}
+
 // grid: NARROW_WG * NARROW_SUB workgroups; lane g = parent g / NARROW_SUB,
 // successors t = g % NARROW_SUB (+ NARROW_SUB ...)
 template <class M>
@@ -245,6 +264,10 @@ k_nexpand(const typename M::State* __restrict__ bufA, const typename M::State* _
   if constexpr (M::CONSTRAINED) {
     if (threadIdx.x < 2) sh_cut[threadIdx.x] = 0;
   }
+  __shared__ unsigned int sh_step[AP_COUNT + 1];   // ActModel: steps violating property k; [AP_COUNT]: steps checked
+  if constexpr (M::STEP_CHECKED) {
+    if (threadIdx.x <= AP_COUNT) sh_step[threadIdx.x] = 0;
+  }
   __syncthreads();
   NarrowLT* __restrict__ lt = sc->lt[lev % NARROW_NLT];
   if (i < n) {
@@ -270,6 +293,8 @@ k_nexpand(const typename M::State* __restrict__ bufA, const typename M::State* _
       M::locate(pl, t, slot, j);
       State x;
       M::apply(s, slot, j, f, x, who);
+      // an action property: every step, before the dedup
+      if constexpr (M::STEP_CHECKED) step_check<M>(s, x, slot, f, &ctl->err[lev & 1], i, t, sh_step);
       // a successor outside the model: no table entry (its
       // hidx slot is never its own: k_nfinish compares the entry's key), its
       // invariants checked here
@@ -299,9 +324,14 @@ k_nexpand(const typename M::State* __restrict__ bufA, const typename M::State* _
     if (threadIdx.x < 2 && sh_cut[threadIdx.x])
       atomicAdd(threadIdx.x ? &stripe(C).cut_action : &stripe(C).cut_state, (unsigned long long)sh_cut[threadIdx.x]);
   }
+  if constexpr (M::STEP_CHECKED) {
+    if (threadIdx.x <= AP_COUNT && sh_step[threadIdx.x])
+      atomicAdd(threadIdx.x < AP_COUNT ? &stripe(C).step_violations[threadIdx.x] : &stripe(C).step_checked,
+                (unsigned long long)sh_step[threadIdx.x]);
+  }
 }
 
-template <bool CON>
+template <bool CON, bool ACT>
 __device__ __forceinline__ void narrow_step(NarrowCtl* __restrict__ ctl, Counters* __restrict__ C, uint64_t total,
                                             unsigned long long cnext, uint32_t lev);
 
@@ -312,9 +342,10 @@ template <class M>
 __device__ __forceinline__ bool lt_enter_succ(NarrowLT* __restrict__ lt, unsigned short* __restrict__ hx,
                                               const typename M::State& x, const typename M::Plan& px, int tx,
                                               unsigned int o, Flags f, NarrowCtl* __restrict__ ctl, unsigned int qq,
-                                              unsigned int* sh_cutn) {
+                                              unsigned int* sh_cutn, unsigned int* sh_stepn) {
   // (ctl, qq, sh_cutn: ConModel only — a cut successor's invariant error is
-  // level L + 1's, its count goes to the workgroup's LDS pair)
+  // level L + 1's, its count goes to the workgroup's LDS pair; sh_stepn:
+  // ActModel only, the same for the steps' action properties)
   bool ok = true;
   const uint64_t foldx = M::fp_fold(x);
   constexpr int NB = 8;
@@ -330,6 +361,7 @@ __device__ __forceinline__ bool lt_enter_succ(NarrowLT* __restrict__ lt, unsigne
         M::locate(px, t0 + q, sl, j);
         typename M::State y;
         M::apply(x, sl, j, f, y, who);
+        if constexpr (M::STEP_CHECKED) step_check<M>(x, y, sl, f, &ctl->err[qq], o, t0 + q, sh_stepn);
         int cut = CUT_NONE;
         if constexpr (M::CONSTRAINED) {
           cut = M::in_model(x, y, sl, f);
@@ -390,6 +422,10 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
   __shared__ unsigned int sh_cutn[2];               // ConModel: level L + 1's cut successors (state / action)
   if constexpr (M::CONSTRAINED) {
     if (threadIdx.x < 2) sh_cutn[threadIdx.x] = 0;
+  }
+  __shared__ unsigned int sh_stepn[AP_COUNT + 1];   // ActModel: level L + 1's violating / checked steps
+  if constexpr (M::STEP_CHECKED) {
+    if (threadIdx.x <= AP_COUNT) sh_stepn[threadIdx.x] = 0;
   }
   if (threadIdx.x == 0) sh_nx = 0;
   if (threadIdx.x < A_COUNT) sh_actn[threadIdx.x] = 0;
@@ -590,7 +626,7 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
           sh_xo[xs] = (unsigned int)o;
           sh_xt[xs] = (unsigned int)tx;
         } else if (!lt_enter_succ<M>(lt_next, sc->hidx[qq], x, px, tx, (unsigned int)o, f, ctl, qq,
-                                     sh_cutn)) {   // LDS full: this lane
+                                     sh_cutn, sh_stepn)) {   // LDS full: this lane
           atomicOr(&ctl->lt_over[qq], 1u);
         }
       }
@@ -653,6 +689,7 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
           M::locate(pxx, t, sl2, j2);
           State y;
           M::apply(xx, sl2, j2, f, y, who2);
+          if constexpr (M::STEP_CHECKED) step_check<M>(xx, y, sl2, f, &ctl->err[qq], (uint64_t)sh_xo[lo], t, sh_stepn);
           int cut = CUT_NONE;
           // a successor outside the model: no table entry;
           // its invariant error and its count are level L + 1's
@@ -696,6 +733,10 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
   if constexpr (M::CONSTRAINED) {
     if (threadIdx.x < 2 && sh_cutn[threadIdx.x]) atomicAdd(&ctl->cut_next[qq][threadIdx.x], sh_cutn[threadIdx.x]);
   }
+  if constexpr (M::STEP_CHECKED) {
+    if (threadIdx.x <= AP_COUNT && sh_stepn[threadIdx.x])
+      atomicAdd(&ctl->step_next[qq][threadIdx.x], sh_stepn[threadIdx.x]);
+  }
   // The last workgroup to get here closes the level.  Its inputs are all
   // device-scope atomics: every wave waits for its own to complete (an
   // s_waitcnt on all counters; no L2 write-back needed), then one returning
@@ -714,7 +755,7 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
   __syncthreads();
   if (sh_last && wv == 0) {
     const unsigned long long all = sh_all;
-    narrow_step<M::CONSTRAINED>(ctl, C, (all >> 28) & ((1ull << 28) - 1), all & ((1ull << 28) - 1), lev);
+    narrow_step<M::CONSTRAINED, M::STEP_CHECKED>(ctl, C, (all >> 28) & ((1ull << 28) - 1), all & ((1ull << 28) - 1), lev);
     NTRACE_F(10);
   }
 }
@@ -722,8 +763,9 @@ k_nfinish(typename M::State* __restrict__ bufA, typename M::State* __restrict__ 
 // Wave 0 of the last k_nfinish workgroup to finish: close level L (its
 // `total` new states with `cnext` successors) and decide about L + 1; lane
 // a commits (L + 1 runs narrow) or drops action a's pre-expansion count
-// (CON, ConModel: lanes 32 and 33 do the same for the two cut counts).
-template <bool CON>
+// (CON, ConModel: lanes 32 and 33 do the same for the two cut counts; ACT,
+// ActModel: lanes 34 to 37 for the step counts).
+template <bool CON, bool ACT>
 __device__ __forceinline__ void narrow_step(NarrowCtl* __restrict__ ctl, Counters* __restrict__ C, uint64_t total,
                                             unsigned long long cnext, uint32_t lev) {
   NarrowCtl& c = *ctl;
@@ -775,6 +817,16 @@ __device__ __forceinline__ void narrow_step(NarrowCtl* __restrict__ ctl, Counter
       if (v) {
         if (keep) atomicAdd(lane == 32 ? &C->s[0].cut_state : &C->s[0].cut_action, (unsigned long long)v);
         c.cut_next[qq][lane - 32] = 0;
+      }
+    }
+  }
+  if constexpr (ACT) {                           // (lanes 34 .. 34 + AP_COUNT: the step counts)
+    if (lane >= 34 && lane <= 34 + AP_COUNT) {
+      const int k = lane - 34;
+      const unsigned int v = __hip_atomic_load(&c.step_next[qq][k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (v) {
+        if (keep) atomicAdd(k < AP_COUNT ? &C->s[0].step_violations[k] : &C->s[0].step_checked, (unsigned long long)v);
+        c.step_next[qq][k] = 0;
       }
     }
   }

@@ -19,6 +19,7 @@ inline Flags flags_of(const kc_model_config& c) {
   f.con_stored = c.constraint_stored;
   f.con_inflight = c.constraint_inflight;
   f.act_con = c.action_constraints;
+  f.act_props = c.action_properties;
   return f;
 }
 

@@ -75,7 +75,10 @@ enum Proc : int { PR_NONE = 0, PR_API, PR_ListAPI };
 enum Ident : int { ID_Secret = 0, ID_PVC = 1 };
 
 // error kinds carried in the low byte of an error key
-enum ErrKind : int { E_NONE = 0, E_ASSERT = 1, E_INVARIANT = 2, E_DEADLOCK = 3 };
+// (E_ACTION_PROPERTY is the largest: of the errors of one (parent, position)
+// an invariant violation wins, as TLC checks a new state's invariants before
+// the implied actions of the step)
+enum ErrKind : int { E_NONE = 0, E_ASSERT = 1, E_INVARIANT = 2, E_DEADLOCK = 3, E_ACTION_PROPERTY = 4 };
 
 // run-time switches (MC.tla constants and build-authored variants)
 //   variant 0 = KubeAPI.tla as written.  Seeded bugs (build-authored, each
@@ -109,7 +112,13 @@ struct Flags {
   int con_stored = -1;
   int con_inflight = -1;
   int act_con = 0;
+  // action properties checked on every step (TLC's PROPERTY [][A]_vars,
+  // DESIGN.md §4.12; read by ActModel only): AP_* bits
+  int act_props = 0;
 };
+// action properties (Flags::act_props, kc_model_config.action_properties)
+constexpr int AP_NO_BLIND_UPDATE = 1, AP_ONE_REPLY_PER_STEP = 2, AP_STORE_NEVER_SHRINKS = 4;
+constexpr int AP_COUNT = 3, AP_ALL = 7;
 // action constraints (Flags::act_con, kc_model_config.action_constraints)
 constexpr int AC_SERVE_CLIENTS_FIRST = 1;
 constexpr int AC_ALL = 1;
@@ -756,6 +765,14 @@ struct Model {
   // the state constraints alone (Init states; action constraints do not apply to Init)
   KC_HD static constexpr int init_in_model(const State&, const Flags&) { return CUT_NONE; }
 
+  // ----------------------------------------------------- action properties
+  // TLC's PROPERTY [][A]_vars: the mask of the properties
+  // (AP_* bits, among Flags::act_props) that the step s -> x violates.  The
+  // plain model checks none; the kernels call the hook only `if constexpr
+  // (M::STEP_CHECKED)`, as they do in_model.  ActModel (below) answers.
+  static constexpr bool STEP_CHECKED = false;
+  KC_HD static constexpr unsigned step_violations(const State&, const State&, int, const Flags&) { return 0; }
+
   // --------------------------------------------------------- fingerprint
   // 64-bit fingerprint of the canonical packed words, normalised the way the
   // FPSet stores it: MSB clear (TLC's disk FPSets reserve it), never 0.
@@ -1248,6 +1265,65 @@ struct ConModel : Model<NC_, NP_, NS_> {
 #define KC_FOR_EACH_CON_MODEL(X) X(1, 1, 1) X(2, 1, 1) X(1, 2, 1) X(1, 3, 1)
 // kc_model_config's constraint fields call for the ConModel instantiation
 inline bool con_active(int stored, int inflight, int act_con) { return stored >= 0 || inflight >= 0 || act_con != 0; }
+
+// The model under action properties (TLC's PROPERTY [][A]_vars, a step
+// invariant; kc_model_config.action_properties): the same
+// states, actions, invariants and fingerprints; step_violations answers, for
+// a step s -> x, which of the properties in Flags::act_props A fails on, and
+// EngineT<ActModel<..>> is the engine's kernel text instantiated once more
+// with the hook's call sites live (engine_act.hip).  A step with x == s
+// passes whatever A says (that is the _vars).  The vocabulary is
+// build-defined:
+//   NoBlindUpdate      every requests[c] that is an Update, "Pending" in s and
+//                      "Ok" in x has some o \in apiState (unprimed) with
+//                      IsVersionOf(o, requests[c].obj) and c \in o.vv (HasRead,
+//                      KubeAPI.tla:733).  It reads no ghost: the stored
+//                      versions are the bits of word 0 inside id_mask.
+//   OneReplyPerStep    at most one of the 2A fields requests[a],
+//                      listRequests[a] leaves "Pending" in the step;
+//   StoreNeverShrinks  Cardinality(apiState') >= Cardinality(apiState), the
+//                      ghost bit excluded (a Delete served violates it: the
+//                      negation asked for a witness).
+template <int NC_, int NP_, int NS_>
+struct ActModel : Model<NC_, NP_, NS_> {
+  using Base = Model<NC_, NP_, NS_>;
+  using Con = ConModel<NC_, NP_, NS_>;
+  using State = typename Base::State;
+  static constexpr bool STEP_CHECKED = true;
+  static constexpr int A = Base::A;
+  // the elements of U whose vv holds reader c
+  static constexpr uint64_t reader_mask(int c) {
+    uint64_t m = 0;
+    for (int u = 0; u < Base::U; ++u)
+      if ((u >> c) & 1) m |= 1ull << u;
+    return m;
+  }
+  KC_HD static unsigned step_violations(const State& s, const State& x, int /*slot*/, const Flags& f) {
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < Base::W; ++k) same &= s.w[k] == x.w[k];
+    if (same || !f.act_props) return 0;
+    unsigned v = 0;
+    if (f.act_props & AP_NO_BLIND_UPDATE) {
+      static_for<A>([&](auto CI) {
+        constexpr int c = CI;
+        constexpr uint64_t RD = reader_mask(c);
+        if (Base::template fld<c>(s, Base::F_RQP, 1) && Base::template fld<c>(s, Base::F_RQOP, 3) == OP_Update &&
+            Base::template fld<c>(s, Base::F_RQST, 2) == ST_Pending && Base::template fld<c>(x, Base::F_RQP, 1) &&
+            Base::template fld<c>(x, Base::F_RQST, 2) == ST_Ok) {
+          const int id = Base::oc_id(Base::template fld<c>(s, Base::F_RQOBJ, Base::OBJB));
+          if (!(s.w[0] & Base::id_mask(id) & RD)) v |= AP_NO_BLIND_UPDATE;
+        }
+      });
+    }
+    if ((f.act_props & AP_ONE_REPLY_PER_STEP) && popc((uint64_t)(Con::pending(s) & ~Con::pending(x))) > 1)
+      v |= AP_ONE_REPLY_PER_STEP;
+    if ((f.act_props & AP_STORE_NEVER_SHRINKS) && Con::stored(x) < Con::stored(s)) v |= AP_STORE_NEVER_SHRINKS;
+    return v;
+  }
+};
+// Models built with action properties: those of KC_FOR_EACH_CON_MODEL
+#define KC_FOR_EACH_ACT_MODEL(X) KC_FOR_EACH_CON_MODEL(X)
 
 // cfg.symmetry restricted to the process sets that have two members or more
 inline int sym_effective(int nc, int np, int symmetry) {

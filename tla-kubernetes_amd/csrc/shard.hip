@@ -1345,6 +1345,10 @@ int kc_shard_create(const kc_model_config* cfg, int rank, int world, kc_shard** 
     set_error("kc_shard_create: constraints are not supported in the sharded loop (single-GPU engine only)");
     return -EINVAL;
   }
+  if (cfg->action_properties) {
+    set_error("kc_shard_create: action properties are not supported in the sharded loop (single-GPU engine only)");
+    return -EINVAL;
+  }
   auto impl = make_shard(*cfg, rank, world);
   if (!impl) {
     set_error("kc_shard_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);

@@ -398,6 +398,10 @@ int kc_sim_create(const kc_model_config* cfg, const kc_sim_config* sim, kc_sim**
     set_error("kc_sim_create: constraints are not supported (the walks step through Next alone)");
     return -EINVAL;
   }
+  if (cfg->action_properties) {
+    set_error("kc_sim_create: action properties are not supported (the walks check invariants only)");
+    return -EINVAL;
+  }
   if (sim->num_walks < 1 || sim->num_walks > KC_SIM_MAX_WALKS) {
     set_error("kc_sim_create: num_walks %llu outside 1..2^30", (unsigned long long)sim->num_walks);
     return -EINVAL;

@@ -410,6 +410,35 @@ int kc_spec_in_model(const kc_model_config* cfg, const uint64_t* tuple_s, const 
   return -EINVAL;
 }
 
+// Action properties (kubeapi_spec.h ActModel::step_violations) on canonical
+// tuples: the mask of cfg->action_properties that the step violates (>= 0).
+int kc_spec_step_violations(const kc_model_config* cfg, const uint64_t* tuple_s, const uint64_t* tuple_x, int action) {
+  if (!cfg || !tuple_s || !tuple_x) { set_error("kc_spec_step_violations: NULL"); return -EINVAL; }
+  if (action < 0 || action >= A_COUNT) {
+    set_error("kc_spec_step_violations: action %d outside 0..%d", action, A_COUNT - 1);
+    return -EINVAL;
+  }
+  if (cfg->action_properties & ~AP_ALL) {
+    set_error("kc_spec_step_violations: action_properties %d outside 0..%d", cfg->action_properties, AP_ALL);
+    return -EINVAL;
+  }
+#define KC_ACT(a, b, c)                                                                      \
+  if (cfg->nc == a && cfg->np == b && cfg->ns == c) {                                        \
+    using M = ActModel<a, b, c>;                                                             \
+    M::State s, x;                                                                           \
+    if (!M::from_tuple(tuple_s, s) || !M::from_tuple(tuple_x, x)) {                          \
+      set_error("kc_spec_step_violations: tuple outside the lowered domain");                \
+      return -EINVAL;                                                                        \
+    }                                                                                        \
+    return (int)M::step_violations(s, x, action == A_APIStart ? 2 * M::A : 0, flags_of(*cfg)); \
+  }
+  KC_FOR_EACH_ACT_MODEL(KC_ACT)
+#undef KC_ACT
+  set_error("kc_spec_step_violations: model nc=%d np=%d ns=%d is not built with action properties", cfg->nc, cfg->np,
+            cfg->ns);
+  return -EINVAL;
+}
+
 int kc_spec_unpack(const kc_model_config* cfg, const uint64_t* packed, uint64_t* tuple) {
   if (!cfg || !packed || !tuple) { set_error("kc_spec_unpack: NULL"); return -EINVAL; }
   return with_model(cfg->nc, cfg->np, cfg->ns, [&](auto m) {

@@ -31,7 +31,7 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from ._lib import (ACTION_CONSTRAINTS, ACTIONS, CKPT_SECTIONS, CUTS, ERR_KINDS, FAIRNESS, INSTANTIATIONS, INVARIANTS,
+from ._lib import (ACTION_CONSTRAINTS, ACTION_PROPERTIES, ACTIONS, CKPT_SECTIONS, CUTS, ERR_KINDS, FAIRNESS, INSTANTIATIONS, INVARIANTS,
                    LIVE_KINDS, PROPERTIES, SIM_KINDS,
                    KcCheckpointInfo, KcCheckpointOptions, KcLiveConfig,
                    KcLiveResult, KcModelConfig, KcResult, KcSimConfig,
@@ -41,7 +41,7 @@ from ._lib import (ACTION_CONSTRAINTS, ACTIONS, CKPT_SECTIONS, CUTS, ERR_KINDS, 
 __all__ = ["ModelConfig", "ModelChecker", "CheckResult", "FPSet", "StateQueue", "Spec",
            "Simulator", "SimResult", "SIM_KINDS", "LivenessChecker", "LiveResult", "PROPERTIES", "FAIRNESS",
            "KubecheckError", "ACTIONS", "load", "device_count", "stress_fps_dev", "stress_fp",
-           "CheckpointInfo", "checkpoint_info"]
+           "CheckpointInfo", "checkpoint_info", "ACTION_PROPERTIES"]
 
 
 def device_count() -> int:
@@ -109,6 +109,29 @@ class ModelConfig:
     constraint_stored: int = -1
     constraint_inflight: int = -1
     action_constraints: Union[int, str, Sequence[str]] = 0
+    # action properties (TLC's PROPERTY [][A]_vars, a step invariant;
+    # DESIGN.md §4.12): checked on every step the BFS generates, into seen
+    # states too.  0 / (), a name of ACTION_PROPERTIES ("NoBlindUpdate",
+    # "OneReplyPerStep", "StoreNeverShrinks"), a sequence of names, or the
+    # mask.  The single-GPU in-HBM BFS only (include/kubecheck.h).
+    action_properties: Union[int, str, Sequence[str]] = 0
+
+    @property
+    def action_properties_mask(self) -> int:
+        a = self.action_properties
+        if isinstance(a, str):
+            a = [a]
+        if isinstance(a, (list, tuple)):
+            m = 0
+            for name in a:
+                if name not in ACTION_PROPERTIES:
+                    raise ValueError(f"action property {name!r}: expected " + ", ".join(ACTION_PROPERTIES))
+                m |= ACTION_PROPERTIES[name]
+            return m
+        a = int(a or 0)
+        if a & ~sum(ACTION_PROPERTIES.values()):
+            raise ValueError(f"action_properties {a}: the mask has bits 0..2 ({', '.join(ACTION_PROPERTIES)})")
+        return a
 
     @property
     def action_constraints_mask(self) -> int:
@@ -149,6 +172,9 @@ class ModelConfig:
                 continue
             if f[0] == "action_constraints":
                 c.action_constraints = self.action_constraints_mask
+                continue
+            if f[0] == "action_properties":
+                c.action_properties = self.action_properties_mask
                 continue
             setattr(c, f[0], int(getattr(self, f[0])))
         # the C string must outlive the engine's use of the config (copied at create)
@@ -198,6 +224,12 @@ class CheckResult:
     claim_mode: str = "minimum"    # the claims that ran: "minimum" (sequential-BFS / rank-major), "first", "tlc"
     cut_state: int = 0             # constraints: successors (and Init states) discarded by a state constraint
     cut_action: int = 0            # ... that passed those and were discarded by an action constraint
+    # action properties: the violated one's name (error == "action_property"),
+    # the steps checked (= generated - init) and, by name, the steps that
+    # violate each, over the levels up to and including the first with one
+    error_property: Optional[str] = None
+    step_checked: int = 0
+    step_violations: Dict[str, int] = field(default_factory=dict)
     trace: List[List[int]] = field(default_factory=list)
     trace_text: str = ""
     # expression-level coverage (run(coverage=True)): base counter name -> its
@@ -210,6 +242,7 @@ class CheckResult:
 
 
 CLAIM_MODES = {0: "minimum", 1: "first", 2: "tlc"}
+_AP_NAMES = {b.bit_length() - 1: n for n, b in ACTION_PROPERTIES.items()}   # bit index -> name
 
 
 def cover_names() -> List[str]:
@@ -228,7 +261,10 @@ def _result(r: KcResult) -> CheckResult:
         error=ERR_KINDS.get(r.err_kind),
         error_action=ACTIONS[r.err_action] if 0 <= r.err_action < len(ACTIONS) else None,
         error_self=r.err_self,
-        error_invariant=INVARIANTS.get(r.err_invariant),
+        error_invariant=INVARIANTS.get(r.err_invariant) if r.err_kind != 4 else None,
+        error_property=_AP_NAMES.get(r.err_invariant) if r.err_kind == 4 else None,
+        step_checked=int(r.step_checked),
+        step_violations={n: int(r.step_violations[b.bit_length() - 1]) for n, b in ACTION_PROPERTIES.items()},
         error_level=r.err_level, trace_len=r.trace_len, seconds=r.seconds,
         collision_optimistic=r.collision_optimistic, fpset_slots=r.fpset_slots,
         peak_frontier=r.peak_frontier, fpset_probes=r.fpset_probes,
@@ -307,8 +343,8 @@ class ModelChecker:
 
     @property
     def instantiation(self) -> str:
-        """The model type the engine was built from: "plain", "symmetry" or
-        "constraints" (a value of INSTANTIATIONS)."""
+        """The model type the engine was built from: "plain", "symmetry",
+        "constraints" or "action_properties" (a value of INSTANTIATIONS)."""
         return INSTANTIATIONS[check("kc_engine_instantiation", self._lib.kc_engine_instantiation(self._h))]
 
     def set_coverage(self, on: bool) -> None:
@@ -960,6 +996,30 @@ class Spec:
         a = ACTIONS.index(action) if isinstance(action, str) else int(action)
         return CUTS[check("kc_spec_in_model", self._lib.kc_spec_in_model(
             C.byref(self._c), None if s is None else _u64(s), _u64(x), a))]
+
+    def step_violations(self, tup_s, tup_x, action) -> int:
+        """The mask of cfg's action properties (ACTION_PROPERTIES bits) that the
+        step tup_s -> tup_x, made by `action` (a name of ACTIONS or its id),
+        violates; 0 when the tuples are equal (host; no GPU)."""
+        s = np.ascontiguousarray(tup_s, dtype=np.uint64)
+        x = np.ascontiguousarray(tup_x, dtype=np.uint64)
+        a = ACTIONS.index(action) if isinstance(action, str) else int(action)
+        return check("kc_spec_step_violations", self._lib.kc_spec_step_violations(C.byref(self._c), _u64(s), _u64(x), a))
+
+    def act_selftest(self, tuples_s, tuples_x, actions) -> np.ndarray:
+        """kc_spec_step_violations' mask for every (parent, successor, action
+        id) triple, computed on the GPU by the device code the engine's
+        kernels call (test harness)."""
+        s = np.ascontiguousarray(tuples_s, dtype=np.uint64).reshape(-1, self.tuple_words)
+        x = np.ascontiguousarray(tuples_x, dtype=np.uint64).reshape(-1, self.tuple_words)
+        a = np.ascontiguousarray(actions, dtype=np.int32)
+        if not (len(s) == len(x) == len(a)):
+            raise ValueError("act_selftest: parents, successors and actions differ in length")
+        out = np.zeros(len(a), dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        check("kc_act_selftest", self._lib.kc_act_selftest(C.byref(self._c), _u64(s), _u64(x), a.ctypes.data_as(ip),
+                                                           len(a), out.ctypes.data_as(ip)))
+        return out
 
     def con_selftest(self, tuples_s, tuples_x, actions) -> np.ndarray:
         """kc_spec_in_model's answer (0 in, 1 state-cut, 2 action-cut) for every

@@ -27,9 +27,12 @@ ACTIONS = [
 ACTION_CONSTRAINTS = {"ServeClientsFirst": 1}
 CUTS = {0: None, 1: "state", 2: "action"}
 # kc_engine_instantiation
-INSTANTIATIONS = {0: "plain", 1: "symmetry", 2: "constraints"}
+INSTANTIATIONS = {0: "plain", 1: "symmetry", 2: "constraints", 3: "action_properties"}
+# action properties (kc_model_config.action_properties bits; a violated one's
+# bit index is kc_result.err_invariant when err_kind is 4)
+ACTION_PROPERTIES = {"NoBlindUpdate": 1, "OneReplyPerStep": 2, "StoreNeverShrinks": 4}
 
-ERR_KINDS = {0: None, 1: "assertion", 2: "invariant", 3: "deadlock"}
+ERR_KINDS = {0: None, 1: "assertion", 2: "invariant", 3: "deadlock", 4: "action_property"}
 INVARIANTS = {0: "TypeOK", 1: "OnlyOneVersion", 2: "NoLostUpdate"}
 
 
@@ -47,6 +50,7 @@ class KcModelConfig(C.Structure):
         ("first_claim", C.c_int),
         ("symmetry", C.c_int),
         ("constraint_stored", C.c_int), ("constraint_inflight", C.c_int), ("action_constraints", C.c_int),
+        ("action_properties", C.c_int),
     ]
 
 
@@ -74,6 +78,7 @@ class KcResult(C.Structure):
         ("defer_redo_level", C.c_uint64), ("narrow_levels", C.c_uint64),
         ("claim_mode", C.c_int),
         ("cut_state", C.c_uint64), ("cut_action", C.c_uint64),
+        ("step_checked", C.c_uint64), ("step_violations", C.c_uint64 * 3),
     ]
 
 
@@ -314,6 +319,8 @@ SIGNATURES = [
     ("kc_spec_in_model", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P, C.c_int]),
     ("kc_con_selftest", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P, _IP, C.c_uint64, _IP]),
     ("kc_engine_instantiation", C.c_int, [_P]),
+    ("kc_spec_step_violations", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P, C.c_int]),
+    ("kc_act_selftest", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P, _IP, C.c_uint64, _IP]),
     ("kc_spec_pack", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
     ("kc_spec_unpack", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),
 ]

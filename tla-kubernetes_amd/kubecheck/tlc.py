@@ -109,6 +109,7 @@ the fairness assumed.  It is refused together with -simulate.
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import os
 import re
 import sys
@@ -130,6 +131,9 @@ SYMMETRY_NAMES = {"SymClients": "clients", "SymControllers": "controllers", "Sym
 CONSTRAINT_FAMILIES = {"StoredAtMost": "constraint_stored", "InFlightAtMost": "constraint_inflight"}
 ACTION_CONSTRAINT_NAMES = ("ServeClientsFirst",)
 KNOWN_CONSTRAINTS = tuple(f + "<k>" for f in CONSTRAINT_FAMILIES) + ACTION_CONSTRAINT_NAMES
+# build-defined action properties (a PROPERTY whose formula is [][A]_vars;
+# there is no TLA+ expression evaluator): the names of kubecheck.ACTION_PROPERTIES
+ACTION_PROPERTY_NAMES = ("NoBlindUpdate", "OneReplyPerStep", "StoreNeverShrinks")
 KNOWN_CONSTANTS = ("REQUESTS_CAN_FAIL", "REQUESTS_CAN_TIMEOUT", "defaultInitValue")  # :4-6,374
 
 
@@ -260,7 +264,24 @@ def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, ch
     checkpointing: one of -checkpoint, -checkpointlevels, -recover was."""
     from ._lib import PROPERTIES
 
-    props = list(cfg["properties"])
+    # a PROPERTY list may mix temporal names (the liveness phase, after a clean
+    # BFS) and action properties ([][A]_vars: checked by the BFS on every step)
+    act_props = [x for x in cfg["properties"] if x in ACTION_PROPERTY_NAMES]
+    props = [x for x in cfg["properties"] if x not in ACTION_PROPERTY_NAMES]
+    if act_props:
+        # action properties: the single-GPU in-HBM BFS alone (DESIGN.md §4.12)
+        names = " ".join(act_props)
+        if cfg.get("constraints") or cfg.get("action_constraints"):
+            raise CfgError(f"action PROPERTY ({names}) with CONSTRAINT / ACTION_CONSTRAINT: not supported together")
+        if cfg.get("symmetry"):
+            raise CfgError(f"action PROPERTY ({names}) with SYMMETRY {cfg['symmetry']}: a step is checked between "
+                           "real states, the seen-set holds orbits")
+        if simulate:
+            raise CfgError(f"action PROPERTY ({names}) with -simulate: the walks check invariants only")
+        if coverage:
+            raise CfgError(f"action PROPERTY ({names}) with -coverage: the coverage counters name none")
+        if checkpointing:
+            raise CfgError(f"action PROPERTY ({names}) with -checkpoint / -recover: a checkpoint names none")
     if cfg.get("constraints") or cfg.get("action_constraints"):
         # constraints: the single-GPU BFS alone (DESIGN.md §4.11)
         names = " ".join(list(cfg.get("constraints") or []) + list(cfg.get("action_constraints") or []))
@@ -289,7 +310,8 @@ def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, ch
                        "so the counts would be no evaluation counts")
     bad = [x for x in props if x not in PROPERTIES]
     if bad:
-        raise CfgError(f"unknown temporal property(ies) {bad}; known: {PROPERTIES}")
+        raise CfgError(f"unknown temporal property(ies) {bad}; known: {PROPERTIES}; "
+                       f"action properties: {ACTION_PROPERTY_NAMES}")
     if props and simulate:
         raise CfgError("-simulate checks no temporal PROPERTY (liveness needs the whole state graph)")
     if cfg.get("symmetry") and props:
@@ -297,7 +319,10 @@ def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, ch
                        "reduction is unsound")
     if cfg.get("symmetry") and simulate:
         raise CfgError(f"SYMMETRY {cfg['symmetry']} with -simulate: a random walk has no seen-set to reduce")
-    return model_from_cfg(dict(cfg, properties=[])), props
+    kw = model_from_cfg(dict(cfg, properties=[]))
+    if act_props:
+        kw["action_properties"] = tuple(dict.fromkeys(act_props))
+    return kw, props
 
 
 def msg(code: int, text: str, cls: int = 0, tool: bool = True) -> str:
@@ -812,6 +837,9 @@ def messages(r, t_start: float, t_end: float, actual_fp_prob: Optional[float] = 
             add(2110, f"Invariant {r.error_invariant} is violated.", 1)
         elif r.error == "assertion":
             add(2132, f"The first argument of Assert evaluated to FALSE (action {r.error_action}).", 1)
+        elif r.error == "action_property":
+            # (the behaviour below is the path to s, then the step's s')
+            add(2112, f"Action property {r.error_property} is violated.", 1)
         else:
             add(2114, "Deadlock reached.", 1)
         add(2121, "The behavior up to this point is:", 1)
@@ -1023,7 +1051,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     except CfgError as e:
         # (a refused combination with the checkpoint flags or with a cfg's
         # constraints ends in an Error line; the older refusals raise, as they did)
-        if not (a.checkpointing or parsed["constraints"] or parsed["action_constraints"]):
+        if not (a.checkpointing or parsed["constraints"] or parsed["action_constraints"] or
+                any(x in ACTION_PROPERTY_NAMES for x in parsed["properties"])):
             raise
         print(f"Error: {e}", file=sys.stderr)
         return 1
@@ -1080,7 +1109,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     rc = 0
     for name in props:
         print(msg(2192, live_start_message(name, a.fairness, r.distinct, time.time()), 0, a.tool), flush=True)
-        with kubecheck.LivenessChecker(mc_cfg, name, fairness=a.fairness) as lc:
+        # (the liveness phase has no part in the action properties: the BFS checked them)
+        with kubecheck.LivenessChecker(dataclasses.replace(mc_cfg, action_properties=0), name,
+                                       fairness=a.fairness) as lc:
             lr = lc.run()
         t1 += lr.seconds
         if lr.error is not None or (lr.states, lr.edges) != (r.distinct, r.generated - r.init):
