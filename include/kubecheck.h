@@ -421,6 +421,41 @@ int kc_engine_set_coverage(kc_engine *e, int on);
  * number written (cap >= kc_cover_count()).  -EINVAL when coverage was off,
  * and after a run that ended in an error (TLC prints no coverage then). */
 int kc_engine_coverage(kc_engine *e, uint64_t *out, int cap);
+/* User-defined invariants.  `program` is n_instr 16-byte
+ * instructions (two uint64_t each; the encoding is csrc/pred.h's, compiled by
+ * kubecheck/pred.py): at most 128 instructions, 8 invariants, nesting depth
+ * 32.  It takes effect from the next run; n_instr = 0 turns it off, and then
+ * the engine allocates and launches what it always did.
+ *
+ * With a program set, run() evaluates every invariant on every state it
+ * expands, Init states included (levels 1..max_levels-1 of a bounded run):
+ * one kernel per chunk next to the engine's own, and one host sync per narrow
+ * level.  The first level that holds a violating state ends the run once that
+ * level's expansion is closed: err_kind = 2, err_invariant = 3 + k (k in the
+ * order given), err_level = that level, and the trace is the parent chain of
+ * the violating state with the smallest index in that level (of the
+ * invariants that state violates, the smallest k is reported).  generated,
+ * distinct and the level widths are whole-level numbers that include that
+ * level's expansion.  A violation at level L comes before anything the
+ * expansion of level L itself found (an Assert, a deadlock, a built-in
+ * invariant violated by a level-L+1 state): TLC would have checked the
+ * level-L state when it was generated.  In the deterministic claim mode a
+ * level's index order is TLC's -workers 1 order, so the state and the trace
+ * are TLC's; in first-claim mode the length is the same and the trace is a
+ * real behaviour.
+ *
+ * -EINVAL, with the reason in kc_last_error: a bad program; an engine under
+ * symmetry reduction; with constraints (TLC checks invariants on the
+ * successors a constraint discards; they are never expanded, so evaluation on
+ * expansion would miss them); with action properties; with coverage on; with
+ * checkpoint or recover; with seen_hbm_bytes, frontier_hbm_bytes or
+ * trace_host. */
+int kc_engine_set_invariants(kc_engine *e, const uint64_t *program, int n_instr);
+/* The last run's states evaluated, then the states violating each invariant
+ * (all zero but for the level that ended the run); returns the number of
+ * words written (1 + invariants).  -EINVAL with no program set or no run
+ * since. */
+int kc_engine_invariant_stats(kc_engine *e, uint64_t *out, int cap);
 /* Per-kernel device timings of the last run (ms; needs cfg.timing=1, or 2
  * for expand alone):
  * expand, resolve, scan, emit; and the number of launches of each. */
@@ -1176,6 +1211,19 @@ int kc_spec_check(const kc_model_config *cfg, const uint64_t *tuple);
  * taken as a state the BFS expands: the host definition of what
  * kc_engine_coverage counts.  sums_out holds kc_cover_count() words. */
 int kc_spec_cover(const kc_model_config *cfg, const uint64_t *tuples, uint64_t n, uint64_t *sums_out);
+/* A predicate program (kc_engine_set_invariants) on one canonical tuple, on
+ * the host through the code k_pred runs: bit k of the result is set when
+ * invariant k is FALSE there.  -EINVAL for a bad program or tuple. */
+int kc_pred_eval(const kc_model_config *cfg, const uint64_t *program, int n_instr, const uint64_t *tuple);
+/* Test-only: k_pred alone on made packed states of W words (4, 6 or 10),
+ * launched as the engine launches it on a chunk that starts at index `base`.
+ * out = KC_EMIT_FORE guard words, the result block (min over the violating
+ * states of (base + i) << 8 | k, or ~0; states evaluated; 8 violation
+ * counts), then the caller's aft guards: uploaded as given and copied back
+ * whole.  The arguments are validated on the host first (-EINVAL needs no
+ * GPU); -ENODEV without one. */
+int kc_pred_selftest(int W, const uint64_t *program, int n_instr, const uint64_t *packed_states, uint64_t n_states,
+                     uint64_t base, uint64_t *out, uint64_t nout);
 int kc_cover_count(void);
 /* Name of counter i, or NULL. */
 const char *kc_cover_name(int i);

@@ -41,6 +41,11 @@ class EngineBase {
   // counters from the next run on; the last run's sums
   virtual int set_coverage(bool on) = 0;
   virtual int coverage(uint64_t* out, int cap) const = 0;
+  // user-defined invariants (pred.h): evaluate the program on
+  // every expanded state from the next run on (n_instr = 0: off); the last
+  // run's states evaluated and violations per invariant
+  virtual int set_invariants(const uint64_t* program, int n_instr) = 0;
+  virtual int invariant_stats(uint64_t* out, int cap) const = 0;
   // checkpoint / recover: write the state the last run
   // stopped with; checkpoint from inside run(); arm the next run to start
   // from a checkpoint

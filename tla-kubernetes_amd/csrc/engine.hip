@@ -25,6 +25,7 @@
 #include "claim_launch.h"
 #include "coldset.h"
 #include "cover.h"
+#include "pred.h"
 #include "engine.h"
 #include "engine_kernels.h"
 #include "engine_narrow.h"
@@ -288,6 +289,7 @@ class EngineT final : public EngineBase {
     }
     rec_armed_ = false;              // (recover() arms one run)
     cover_valid_ = cover_on_ && rc == 0 && res->err_kind == 0;
+    pred_valid_ = pred_on_ && rc == 0;
     return rc;
   }
 
@@ -314,6 +316,11 @@ class EngineT final : public EngineBase {
     }
     if (on && (ck_on_ || rec_armed_)) {
       set_error("kc_engine_set_coverage: not with checkpointing (a checkpoint holds no coverage sums)");
+      return -EINVAL;
+    }
+    if (on && pred_on_) {
+      set_error("kc_engine_set_coverage: not with user invariants (kc_engine_set_invariants; a run that ends at a "
+                "violation has no coverage to report)");
       return -EINVAL;
     }
     cover_on_ = on;
@@ -362,6 +369,116 @@ class EngineT final : public EngineBase {
     while (!cover_levels_.empty() && cover_levels_.back().first >= level) cover_levels_.pop_back();
   }
 
+  // ---- user-defined invariants (pred.h).  k_pred runs where
+  // k_cover runs: over each expanded level's parents while they are resident
+  // in cur_.  A level's result block goes to the host at the level's own sync
+  // and counts once the level is closed (a level the deferred frontier redoes
+  // is dropped first); the first level with a violating state ends the run.
+  int set_invariants(const uint64_t* program, int n_instr) override {
+    if (n_instr == 0) {
+      pred_on_ = false;
+      pred_valid_ = false;
+      pred_prog_.clear();
+      return 0;
+    }
+    const char* why = nullptr;
+    if (!program) why = "NULL program";
+    else if (M::CONSTRAINED)
+      why = "not with constraints (TLC checks invariants on the successors a constraint discards; they are never "
+            "expanded, so this evaluation on expansion would miss them)";
+    else if (M::STEP_CHECKED) why = "not with action properties";
+    else if (!std::is_same<Model<M::NC, M::NP, M::NS>, M>::value)
+      why = "not under symmetry reduction (a predicate that names a process is not orbit-invariant)";
+    else if (spill_ || queued_ || cfg_.trace_host)
+      why = "not with seen_hbm_bytes, frontier_hbm_bytes or trace_host";
+    else if (ablate_) why = "not with KC_ABLATE";
+    else if (cover_on_) why = "not with coverage on (kc_engine_set_coverage)";
+    else if (ck_on_ || rec_armed_) why = "not with checkpoint or recover (a checkpoint holds no invariant counts)";
+    if (why) {
+      set_error("kc_engine_set_invariants: %s", why);
+      return -EINVAL;
+    }
+    const PredInstr* code = reinterpret_cast<const PredInstr*>(program);
+    const int ninv = pred_validate(code, n_instr, M::W, &why);
+    if (ninv < 0) {
+      set_error("kc_engine_set_invariants: bad program (at most %d instructions, %d invariants, nesting depth %d): %s",
+                KC_PRED_MAX_INSTR, KC_PRED_MAX_INV, KC_PRED_MAX_DEPTH, why);
+      return -EINVAL;
+    }
+    pred_prog_.assign(code, code + n_instr);
+    pred_ninv_ = ninv;
+    pred_on_ = true;
+    pred_valid_ = false;
+    return 0;
+  }
+  int invariant_stats(uint64_t* out, int cap) const override {
+    if (!pred_on_) {
+      set_error("kc_engine_invariant_stats: no user invariants are set (kc_engine_set_invariants)");
+      return -EINVAL;
+    }
+    if (!out || cap < 1 + pred_ninv_) {
+      set_error("kc_engine_invariant_stats: NULL or fewer than %d words", 1 + pred_ninv_);
+      return -EINVAL;
+    }
+    if (!pred_valid_) {
+      set_error("kc_engine_invariant_stats: no run since kc_engine_set_invariants (or the last one failed)");
+      return -EINVAL;
+    }
+    for (int k = 0; k < 1 + pred_ninv_; ++k) out[k] = 0;
+    for (const auto& lv : pred_levels_)
+      for (int k = 0; k < 1 + pred_ninv_; ++k) out[k] += lv.second[1 + k];
+    return 1 + pred_ninv_;
+  }
+  int pred_begin() {
+    pred_levels_.clear();
+    if (!pred_on_) return 0;
+    KC_TRY(d_pred_prog_.alloc(KC_PRED_MAX_INSTR));
+    KC_TRY(d_pred_.alloc(PRED_OUT_WORDS));
+    KC_TRY(h_pred_.alloc(PRED_OUT_WORDS));
+    KC_HIP_TRY(hipMemcpyAsync(d_pred_prog_, pred_prog_.data(), pred_prog_.size() * sizeof(PredInstr),
+                              hipMemcpyHostToDevice, st_));
+    return pred_reset(d_pred_.p, st_);
+  }
+  // parents [start, start + cn) of the level in cur_
+  int pred_count(uint64_t start, uint64_t cn) {
+    return pred_launch(M::W, cur_.p + start, cn, start, d_pred_prog_.p, (int)pred_prog_.size(), d_pred_.p, st_);
+  }
+  // the level's block to the host and the device block reset (enqueued; valid after the next sync)
+  int pred_fetch() {
+    KC_HIP_TRY(hipMemcpyAsync(h_pred_, d_pred_, PRED_OUT_WORDS * 8, hipMemcpyDeviceToHost, st_));
+    return pred_reset(d_pred_.p, st_);
+  }
+  void pred_commit(int level) {
+    std::array<uint64_t, PRED_OUT_WORDS> v;
+    for (int k = 0; k < PRED_OUT_WORDS; ++k) v[k] = h_pred_[k];
+    pred_levels_.emplace_back(level, v);
+  }
+  void pred_drop_from(int level) {
+    while (!pred_levels_.empty() && pred_levels_.back().first >= level) pred_levels_.pop_back();
+  }
+  // the level just committed holds a violating state: the report (the parent
+  // chain of the smallest index, the smallest k it violates)
+  bool pred_violated() const { return !pred_levels_.empty() && pred_levels_.back().second[0] != ~0ull; }
+  int pred_report(kc_result* res, int level, uint64_t level_gidx, uint64_t n) {
+    const uint64_t key = pred_levels_.back().second[0];
+    const uint64_t idx = key >> 8;
+    if (idx >= n || (int)(key & 0xff) >= pred_ninv_) {
+      set_error("kubecheck: bad user-invariant key");
+      return -EIO;
+    }
+    res->err_kind = E_INVARIANT;
+    res->err_invariant = 3 + (int)(key & 0xff);
+    res->err_level = level;
+    res->err_action = res->err_self = -1;
+    if (cfg_.keep_trace) {
+      std::vector<State> path;
+      KC_TRY(path_to(level_gidx + idx, path));
+      trace_ = path;
+      res->trace_len = (int)path.size();
+    }
+    return 0;
+  }
+
   // Where the BFS stands at the top of a level.
   // Deferred frontier (defer_now_): `mat` = cur_ holds this level's states.
   // Otherwise the level's k_claim rebuilds them from the previous frontier
@@ -385,6 +502,7 @@ class EngineT final : public EngineBase {
     if (M::STEP_CHECKED) return "not with action properties (a checkpoint header names none)";
     if (spill_ || queued_ || cfg_.trace_host) return "not with seen_hbm_bytes, frontier_hbm_bytes or trace_host";
     if (cover_on_) return "not with coverage on (a checkpoint holds no coverage sums)";
+    if (pred_on_) return "not with user invariants (a checkpoint holds no invariant counts)";
     if (ablate_) return "not with KC_ABLATE";
     return nullptr;
   }
@@ -711,6 +829,7 @@ class EngineT final : public EngineBase {
     KC_HIP_TRY(hipSetDevice(cfg_.device));
     reset_run(res);
     KC_TRY(cover_begin());
+    KC_TRY(pred_begin());
     LevelCursor c;
     std::vector<State> init;
     int rc = rec_armed_ ? restore_run(res, c) : seed_init(res, c, init);
@@ -950,16 +1069,30 @@ class EngineT final : public EngineBase {
     int stop = cfg_.max_levels;
     if (capture_level_ >= c.level + 1 && (stop == 0 || capture_level_ - 1 < stop)) stop = capture_level_ - 1;
     // coverage: one level per run, counted from cur_ before the run expands it
-    if (cover_on_ && (stop == 0 || c.level + 1 < stop)) stop = c.level + 1;
+    if ((cover_on_ || pred_on_) && (stop == 0 || c.level + 1 < stop)) stop = c.level + 1;
     // a checkpoint by levels: the run stops at the top of the next level due
     if (ck_on_ && ck_every_ > 0) {
       const int due = c.level + ck_every_ - (c.level - ck_l0_) % ck_every_;
       if (stop == 0 || due < stop) stop = due;
     }
     const int level0 = c.level;
-    const uint64_t n0 = c.n;
+    const uint64_t n0 = c.n, gidx0 = c.level_gidx;
     NarrowRun nr;
     KC_TRY(run_narrow(c, stop, nr));
+    bool pred_bad = false;
+    if (pred_on_ && nr.counted) {
+      // (as coverage below: a run that took no level leaves it to the wide path, which evaluates it again)
+      KC_TRY(pred_fetch());
+      KC_HIP_TRY(hipStreamSynchronize(st_));
+      if (nr.levels > 1) {
+        set_error("kubecheck: user invariants: the narrow kernel ran %d levels in one run", nr.levels);
+        return -EIO;
+      }
+      if (nr.levels == 1) {
+        pred_commit(level0);
+        pred_bad = pred_violated();
+      }
+    }
     if (cover_on_ && nr.counted) {
       // (a run that took no level leaves it to the wide path, which counts it again)
       KC_TRY(cover_fetch());
@@ -980,6 +1113,19 @@ class EngineT final : public EngineBase {
     }
     if (nr.levels) res->peak_frontier = std::max<uint64_t>(res->peak_frontier, std::max(n0, nr.peak));
     if (nr.levels) res->nlevels = c.n ? c.level : c.level - 1;
+    if (pred_bad) {
+      // the level's own violation comes before anything its expansion found
+      // (an NX_ERROR included, which leaves the next level's width unrecorded);
+      // the counts are the whole level's, the width of what it found included
+      res->nlevels = level0;
+      if (nr.new_total && level0 < KC_MAX_LEVELS) {
+        res->level_width[level0] = nr.new_total;
+        res->nlevels = level0 + 1;
+      }
+      KC_TRY(pred_report(res, level0, gidx0, n0));
+      finish(res, 0);
+      return kRunDone;
+    }
     if (defer_now_ && nr.levels && nr.reason != NX_ERROR) KC_TRY(counter_snap(c.level - 1));
     if (nr.reason == NX_ERROR) {
       KC_TRY(report_error(res, h_ns_->err_key, c.level, c.level_gidx, c.n));
@@ -1090,6 +1236,7 @@ class EngineT final : public EngineBase {
     if (ablate_) KC_TRY(ablate_claims(start, cn, tiles, succ_level));
     // coverage: the chunk's parents are in cur_ (a deferred level's k_claim has just rebuilt and stored them)
     if (cover_on_) KC_TRY(cover_count(start, cn));
+    if (pred_on_) KC_TRY(pred_count(start, cn));
     // (a small chunk: the overflow list's pass B inside the tile scan's launch)
     const bool fuse = tscan_ && cn <= FUSE_OVF_SCAN_MAX && !first_claim_;
     if (!first_claim_)
@@ -1176,6 +1323,7 @@ class EngineT final : public EngineBase {
       hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(64), 0, st_, d_ctr_.p);   // next level's head
     }
     if (cover_on_) KC_TRY(cover_fetch());
+    if (pred_on_) KC_TRY(pred_fetch());
     KC_HIP_TRY(hipStreamSynchronize(st_));
     collect_times();
     const Counters& h = *h_ctr_;
@@ -1210,6 +1358,7 @@ class EngineT final : public EngineBase {
       const uint64_t dc_here = h.cand_total - c.cand_total;
       if (!redo_from(X, dc_here, res, c)) return kDeferRetry;
       cover_drop_from(X);            // levels X.. run again and are counted then
+      pred_drop_from(X);
       pc_valid_ = false;
       return 0;
     }
@@ -1220,6 +1369,17 @@ class EngineT final : public EngineBase {
     const uint64_t n_new = h.chunk_base;
     cs_.count = spill_ ? hot_count_ : cs_.count + n_new;
     res->peak_frontier = std::max<uint64_t>(res->peak_frontier, c.n);
+    if (pred_on_) {
+      // this level's own violation comes before anything its expansion found
+      pred_commit(c.level);
+      if (pred_violated()) {
+        KC_TRY(pred_report(res, c.level, c.level_gidx, c.n));
+        res->distinct += n_new;
+        KC_TRY(record_level(res, c.level + 1, n_new));
+        finish(res, 0);
+        return kRunDone;
+      }
+    }
     if (h.err_key != ~0ull) {
       KC_TRY(report_error(res, h.err_key, c.level, c.level_gidx, c.n));
       res->distinct += n_new;
@@ -1680,6 +1840,10 @@ class EngineT final : public EngineBase {
       KC_TRY(cover_count(0, n));
       nr.counted = true;
     }
+    if (pred_on_) {
+      KC_TRY(pred_count(0, n));
+      nr.counted = true;
+    }
     // the run's first level is expanded on its own; every k_nfinish then
     // expands the states it emits for the level after it
     hipLaunchKernelGGL(k_nexpand<M>, dim3(NARROW_WG * NARROW_SUB), dim3(NARROW_THREADS), 0, st_, a, b, flags_,
@@ -1691,7 +1855,7 @@ class EngineT final : public EngineBase {
       // profiles/r06g_model1_narrow_graph_ab.log)
       timed(KK_NARROW, [&] {
         // (coverage: the run stops after its first level, which one k_nfinish closes)
-        for (int k = 0; k < (cover_on_ ? 1 : narrow_batch_); ++k, ++lev)
+        for (int k = 0; k < (cover_on_ || pred_on_ ? 1 : narrow_batch_); ++k, ++lev)
           hipLaunchKernelGGL(k_nfinish<M>, dim3(NARROW_FWG), dim3(NARROW_THREADS), 0, st_, a, b, flags_,
                              cfg_.check_deadlock, tf_.parent(), tf_.ord(), cfg_.keep_trace, lev, d_ns_.p, d_nsc_.p,
                              cs_.t, cs_.nslots, d_ctr_.p, d_ntrace_.p, cs_.word_shift());
@@ -2254,6 +2418,15 @@ class EngineT final : public EngineBase {
   Flags flags_{};
   uint64_t init_cut_ = 0;       // Init states discarded by a state constraint (ConModel)
   bool cover_on_ = false, cover_valid_ = false;
+  // user-defined invariants: the program (host copy and the run's device
+  // copy), the current level's result block and the closed levels' blocks
+  bool pred_on_ = false, pred_valid_ = false;
+  int pred_ninv_ = 0;
+  std::vector<PredInstr> pred_prog_;
+  DeviceArray<PredInstr> d_pred_prog_;
+  DeviceArray<unsigned long long> d_pred_;
+  PinnedArray<unsigned long long> h_pred_;
+  std::vector<std::pair<int, std::array<uint64_t, PRED_OUT_WORDS>>> pred_levels_;   // (level, its block)
   DeviceArray<unsigned long long> d_cover_;      // the current level's sums
   PinnedArray<unsigned long long> h_cover_;
   std::vector<std::pair<int, std::array<uint64_t, KC_COVER_N>>> cover_levels_;   // (level, its sums), closed levels
@@ -2522,6 +2695,17 @@ int kc_engine_capture_level(kc_engine* e, int level) {
 int kc_engine_set_coverage(kc_engine* e, int on) {
   if (!e) { set_error("kc_engine_set_coverage: NULL"); return -EINVAL; }
   return e->impl->set_coverage(on != 0);
+}
+
+int kc_engine_set_invariants(kc_engine* e, const uint64_t* program, int n_instr) {
+  if (!e) { set_error("kc_engine_set_invariants: NULL"); return -EINVAL; }
+  if (n_instr < 0) { set_error("kc_engine_set_invariants: negative n_instr"); return -EINVAL; }
+  return e->impl->set_invariants(program, n_instr);
+}
+
+int kc_engine_invariant_stats(kc_engine* e, uint64_t* out, int cap) {
+  if (!e) { set_error("kc_engine_invariant_stats: NULL"); return -EINVAL; }
+  return e->impl->invariant_stats(out, cap);
 }
 
 int kc_engine_coverage(kc_engine* e, uint64_t* out, int cap) {

@@ -37,11 +37,12 @@ from ._lib import (ACTION_CONSTRAINTS, ACTION_PROPERTIES, ACTIONS, CKPT_SECTIONS
                    KcLiveResult, KcModelConfig, KcResult, KcSimConfig,
                    KcSimResult, KcSqueueConfig, KcSqueueStats, KubecheckError,
                    check, load)
+from . import pred
 
 __all__ = ["ModelConfig", "ModelChecker", "CheckResult", "FPSet", "StateQueue", "Spec",
            "Simulator", "SimResult", "SIM_KINDS", "LivenessChecker", "LiveResult", "PROPERTIES", "FAIRNESS",
            "KubecheckError", "ACTIONS", "load", "device_count", "stress_fps_dev", "stress_fp",
-           "CheckpointInfo", "checkpoint_info", "ACTION_PROPERTIES"]
+           "CheckpointInfo", "checkpoint_info", "ACTION_PROPERTIES", "pred", "UserInvariant"]
 
 
 def device_count() -> int:
@@ -187,6 +188,14 @@ class ModelConfig:
 
 
 @dataclass
+class UserInvariant:
+    """One user-defined invariant of a run (ModelChecker(invariants=...))."""
+    name: str
+    violations: int          # states violating it in the level that ended the run (0 when it holds)
+    states_evaluated: int    # states the run expanded, each evaluated once
+
+
+@dataclass
 class CheckResult:
     init: int
     generated: int
@@ -235,6 +244,8 @@ class CheckResult:
     # expression-level coverage (run(coverage=True)): base counter name -> its
     # sum over the states expanded; None when off or after an error
     coverage: Optional[Dict[str, int]] = None
+    # user-defined invariants (ModelChecker(invariants=...)), in the order given
+    user_invariants: List[UserInvariant] = field(default_factory=list)
 
     @property
     def distinct_per_sec(self) -> float:
@@ -330,7 +341,10 @@ def checkpoint_info(dir: str) -> CheckpointInfo:
 class ModelChecker:
     """BFS safety checker (TLC's ModelChecker for this spec) on one GPU."""
 
-    def __init__(self, cfg: Optional[ModelConfig] = None, *, coverage: bool = False, **kw):
+    def __init__(self, cfg: Optional[ModelConfig] = None, *, coverage: bool = False,
+                 invariants: Optional[Dict[str, str]] = None, **kw):
+        """invariants: {name: predicate text} (kubecheck.pred), checked on
+        every state the run expands next to the cfg's built-in ones."""
         self.cfg = cfg or ModelConfig(**kw)
         self._lib = load()
         self._h = C.c_void_p()
@@ -338,8 +352,11 @@ class ModelChecker:
         check("kc_engine_create", self._lib.kc_engine_create(C.byref(self._c), C.byref(self._h)))
         self.tuple_words = self._lib.kc_spec_tuple_words(self.cfg.nc, self.cfg.np, self.cfg.ns)
         self._coverage = False
+        self._user_invariants: List[str] = []
         if coverage:
             self.set_coverage(True)
+        if invariants:
+            self.set_invariants(invariants)
 
     @property
     def instantiation(self) -> str:
@@ -353,6 +370,21 @@ class ModelChecker:
         check("kc_engine_set_coverage", self._lib.kc_engine_set_coverage(self._h, int(bool(on))))
         self._coverage = bool(on)
 
+    def set_invariants(self, invariants: Optional[Dict[str, str]]) -> None:
+        """Compile {name: predicate text or AST} for this model and check them in
+        the runs that follow (at most 8; None or {} turns them off).  Raises
+        pred.PredError for a predicate that does not compile, KubecheckError
+        where the engine refuses (symmetry, constraints, action properties,
+        coverage, checkpoints, the spill options)."""
+        if not invariants:
+            check("kc_engine_set_invariants", self._lib.kc_engine_set_invariants(self._h, None, 0))
+            self._user_invariants = []
+            return
+        prog = pred.compile_invariants(invariants, self.cfg.nc, self.cfg.np, self.cfg.ns)
+        words = (C.c_uint64 * len(prog.words))(*prog.words)
+        check("kc_engine_set_invariants", self._lib.kc_engine_set_invariants(self._h, words, prog.n_instr))
+        self._user_invariants = list(prog.names)
+
     def capture_level(self, level: int) -> None:
         check("kc_engine_capture_level", self._lib.kc_engine_capture_level(self._h, level))
 
@@ -363,6 +395,14 @@ class ModelChecker:
         r = KcResult()
         check("kc_engine_run", self._lib.kc_engine_run(self._h, C.byref(r)))
         res = _result(r)
+        if self._user_invariants:
+            n = 1 + len(self._user_invariants)
+            out = (C.c_uint64 * n)()
+            check("kc_engine_invariant_stats", self._lib.kc_engine_invariant_stats(self._h, out, n))
+            res.user_invariants = [UserInvariant(name, int(out[1 + k]), int(out[0]))
+                                   for k, name in enumerate(self._user_invariants)]
+            if r.err_kind == 2 and r.err_invariant >= 3:
+                res.error_invariant = self._user_invariants[r.err_invariant - 3]
         if self._coverage and res.error is None:
             n = self._lib.kc_cover_count()
             out = (C.c_uint64 * n)()
@@ -937,6 +977,18 @@ class Spec:
         out = (C.c_uint64 * n)()
         check("kc_spec_cover", self._lib.kc_spec_cover(C.byref(self._c), _u64(t), t.shape[0], out))
         return {k: int(out[i]) for i, k in enumerate(cover_names())}
+
+    def eval_invariant(self, expr, tuples) -> np.ndarray:
+        """A user-defined invariant (predicate text or AST) on canonical tuples
+        (n x tuple_words), compiled and run on the host through the code k_pred
+        runs: one bool per tuple, True where it holds."""
+        prog = pred.compile_invariants([expr], self.cfg.nc, self.cfg.np, self.cfg.ns)
+        words = (C.c_uint64 * len(prog.words))(*prog.words)
+        t = np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, self.tuple_words)
+        out = np.zeros(t.shape[0], dtype=bool)
+        for i in range(t.shape[0]):
+            out[i] = check("kc_pred_eval", self._lib.kc_pred_eval(C.byref(self._c), words, prog.n_instr, _u64(t[i]))) == 0
+        return out
 
     def check_invariants(self, tup) -> Optional[str]:
         t = np.ascontiguousarray(tup, dtype=np.uint64)

@@ -227,6 +227,8 @@ SIGNATURES = [
     ("kc_engine_capture_level", C.c_int, [_P, C.c_int]),
     ("kc_engine_set_coverage", C.c_int, [_P, C.c_int]),
     ("kc_engine_coverage", C.c_int, [_P, _U64P, C.c_int]),
+    ("kc_engine_set_invariants", C.c_int, [_P, _U64P, C.c_int]),
+    ("kc_engine_invariant_stats", C.c_int, [_P, _U64P, C.c_int]),
     ("kc_engine_kernel_times", C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
     ("kc_engine_narrow_times", C.c_int, [_P, C.POINTER(C.c_double), _U64P, _U64P]),
     ("kc_engine_check_fps", C.c_int, [_P, _U64P, C.POINTER(C.c_double)]),
@@ -308,6 +310,8 @@ SIGNATURES = [
     ("kc_spec_successors", C.c_int, [C.POINTER(KcModelConfig), _U64P, _IP, _U64P, C.c_int, _IP]),
     ("kc_spec_check", C.c_int, [C.POINTER(KcModelConfig), _U64P]),
     ("kc_spec_cover", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_uint64, _U64P]),
+    ("kc_pred_eval", C.c_int, [C.POINTER(KcModelConfig), _U64P, C.c_int, _U64P]),
+    ("kc_pred_selftest", C.c_int, [C.c_int, _U64P, C.c_int, _U64P, C.c_uint64, C.c_uint64, _U64P, C.c_uint64]),
     ("kc_cover_count", C.c_int, []),
     ("kc_cover_name", C.c_char_p, [C.c_int]),
     ("kc_spec_fingerprint", C.c_int, [C.POINTER(KcModelConfig), _U64P, _U64P]),

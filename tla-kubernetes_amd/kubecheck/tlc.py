@@ -101,6 +101,17 @@ checkpoint output: the codes and wording are recalled from TLC's message
 table and claim no match.  These flags together with -simulate, a PROPERTY
 list or -coverage are an error.
 
+User-defined invariants: `-defs FILE` names a file of `Name == expr`
+definitions (kubecheck.pred's language: TLA+-flavoured predicates over the
+spec's variables; an expression may span lines up to the next `Name ==`
+line).  An INVARIANT name of the cfg that is defined there is compiled to a
+predicate program and checked on the GPU on every state the BFS expands
+(DESIGN.md §4.13); a violation prints what a built-in one prints (2110
+"Invariant Name is violated." and the behaviour).  A name found nowhere is the
+unknown-invariant error it always was.  A user invariant with -simulate, a
+PROPERTY list, SYMMETRY, CONSTRAINT / ACTION_CONSTRAINT, -coverage or the
+checkpoint flags is an error (models/Reach.cfg, models/Reach.tla).
+
 `-fairness process` checks the properties under weak
 fairness of every process (PlusCal's `fair process`; a .cfg cannot say this,
 so it is an option) instead of WF_vars(Next), the default; the 2192 line names
@@ -255,6 +266,42 @@ def model_from_cfg(cfg: dict) -> dict:
         raise CfgError(f"CONSTRAINT / ACTION_CONSTRAINT with SYMMETRY {cfg['symmetry']}: TLC needs a symmetric "
                        "constraint, and these would each need an argument")
     return kw
+
+
+def split_user_invariants(cfg: dict, defs: Optional[Dict[str, str]], procs=(1, 1, 1), simulate: bool = False,
+                          coverage: bool = False, checkpointing: bool = False):
+    """Take the INVARIANT names that `defs` (-defs FILE: name -> predicate
+    text) defines out of a parsed cfg: (the cfg without them, {name: text} in
+    cfg order).  A name that is neither built in nor defined stays, and
+    model_from_cfg reports it as it always did.  The predicates are compiled
+    here (no GPU), so a bad one is a CfgError before anything runs."""
+    from . import pred
+
+    builtin = KNOWN_INVARIANTS + BUILD_INVARIANTS
+    user = {x: defs[x] for x in cfg["invariants"] if x not in builtin and defs and x in defs}
+    if not user:
+        return cfg, {}
+    names = " ".join(user)
+    if simulate:
+        raise CfgError(f"user-defined INVARIANT ({names}) with -simulate: the walks check the built-in invariants only")
+    if cfg["properties"]:
+        raise CfgError(f"user-defined INVARIANT ({names}) with a PROPERTY list: not supported together")
+    if cfg.get("symmetry"):
+        raise CfgError(f"user-defined INVARIANT ({names}) with SYMMETRY {cfg['symmetry']}: a predicate that names a "
+                       "process is not orbit-invariant")
+    if cfg.get("constraints") or cfg.get("action_constraints"):
+        raise CfgError(f"user-defined INVARIANT ({names}) with CONSTRAINT / ACTION_CONSTRAINT: TLC checks invariants on "
+                       "the successors a constraint discards; they are never expanded here, so they would be missed")
+    if coverage:
+        raise CfgError(f"user-defined INVARIANT ({names}) with -coverage: not supported together")
+    if checkpointing:
+        raise CfgError(f"user-defined INVARIANT ({names}) with -checkpoint / -recover: a checkpoint holds no "
+                       "invariant counts")
+    try:
+        pred.compile_invariants(user, *procs)
+    except pred.PredError as e:
+        raise CfgError(f"user-defined INVARIANT {e}") from None
+    return dict(cfg, invariants=[x for x in cfg["invariants"] if x not in user]), user
 
 
 def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, checkpointing: bool = False):
@@ -994,6 +1041,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                     help="-simulate: run every behaviour to its end after an error")
     ap.add_argument("spec", nargs="?", default="MC")
     ap.add_argument("-config", default=None)
+    ap.add_argument("-defs", default=None, metavar="FILE",
+                    help="`Name == expr` definitions of user invariants the cfg's INVARIANT list may name")
     ap.add_argument("-deadlock", action="store_true", help="do NOT check for deadlock (TLC flag)")
     ap.add_argument("-tool", action="store_true")
     ap.add_argument("-workers", default="1")
@@ -1046,6 +1095,18 @@ def main(argv: Optional[List[str]] = None) -> int:
     tla_path = os.path.join(os.path.dirname(os.path.abspath(cfg_path)), f"{a.spec}.tla")
     defs = parse_defs(open(tla_path).read()) if os.path.exists(tla_path) else {}
     parsed = parse_cfg(open(cfg_path).read(), defs)
+    user_inv = {}
+    if a.defs:
+        from . import pred
+        if not os.path.exists(a.defs):
+            print(f"Error: cannot read the definitions {a.defs}", file=sys.stderr)
+            return 1
+        try:
+            user_defs = pred.parse_definitions(open(a.defs).read())
+        except pred.PredError as e:
+            raise CfgError(f"-defs {a.defs}: {e}") from None
+        parsed, user_inv = split_user_invariants(parsed, user_defs, (a.nc, a.np, a.ns), a.simulate, a.coverage,
+                                                 a.checkpointing)
     try:
         kw, props = check_from_cfg(parsed, a.simulate, a.coverage, a.checkpointing)
     except CfgError as e:
@@ -1077,6 +1138,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     metadir = a.metadir or a.recover or os.path.join(os.path.dirname(os.path.abspath(cfg_path)), "states")
     with kubecheck.ModelChecker(mc_cfg, coverage=a.coverage) as mc:
         try:
+            if user_inv:
+                mc.set_invariants(user_inv)
             if a.recover:
                 mc.recover(a.recover)
                 recovered = (a.recover.rstrip("/"), kubecheck.checkpoint_info(a.recover))
