@@ -836,9 +836,25 @@ int kc_sim_replay(const kc_model_config *cfg, uint64_t seed, int depth, uint64_t
  * involved); the invariants are not evaluated.  A state whose Next raises an
  * Assert ends the build: err_kind = 1 and no verdict (kc_engine_* is the tool
  * for safety).  max_states sizes every buffer at create (the edge buffer holds
- * 8 per state); a larger graph ends kc_live_run with -ENOMEM. */
+ * 8 per state); a larger graph ends kc_live_run with -ENOMEM.
+ *
+ * User formulas (property = KC_LIVE_USER and kc_live_create_formula): two state
+ * predicates P and Q as one predicate program (kc_engine_set_invariants'
+ * format; END 0 = P, END 1 = Q) and a form.  Every form reduces to the stay
+ * question above plus a trigger set T:
+ *   form 0   P ~> Q, [](P => <>Q)   stay = ~Q   T = the states where P holds
+ *            []<>Q                  the same with P = TRUE
+ *   form 1   <>Q                    stay = ~Q   T = the Init states
+ * L is computed from alive = stay exactly as above, under either fairness; the
+ * property is violated iff L and T share a state, and the counterexample is
+ * the shortest prefix to the state of L /\ T with the smallest discovery index,
+ * then the same lasso from it (L is closed under "can stay in L for ever").
+ * The built-in properties are the case T = every state.  A user formula places
+ * no nc = 1 requirement.  <>[]Q is not of this shape (it needs an acceptance
+ * condition on the SCCs of the whole graph) and []P is an invariant. */
+#define KC_LIVE_USER (-1)
 typedef struct {
-  int property;              /* 0 .. 3, above */
+  int property;              /* 0 .. 3, above; KC_LIVE_USER: with kc_live_create_formula only */
   uint64_t max_states;       /* 0 = 2^24; 16 .. 2^27 */
   int fairness;              /* 0 WF_vars(Next), 1 per process; else -EINVAL */
 } kc_live_config;
@@ -848,7 +864,7 @@ typedef struct {
   uint64_t stay_states, live_states, live_terminal; /* |S|, |L|, terminal states in L */
   uint64_t rounds;              /* trim launches, the last (empty) one included */
   int err_kind, err_action, err_self; /* an Assert met while building the graph */
-  int violated;                 /* 1 iff |L| > 0 */
+  int violated;                 /* 1 iff |L| > 0; a user formula: iff |L /\ T| > 0 */
   int kind;                     /* 0 none, 1 back-to-state, 2 stuttering */
   int prefix_len;               /* states up to and including the first L state */
   int trace_len, loop_start;    /* states in the counterexample; 0-based index the last
@@ -867,6 +883,22 @@ typedef struct kc_live kc_live;
 int kc_live_create(const kc_model_config *cfg, const kc_live_config *live, kc_live **out);
 void kc_live_destroy(kc_live *l);
 int kc_live_run(kc_live *l, kc_live_result *res);
+/* kc_live_create for a user formula: live->property must be KC_LIVE_USER
+ * (kc_live_create itself keeps refusing that value: a handle never lacks its
+ * formula).  form 0 = leads-to, 1 = eventually (above); program = n_instr
+ * instructions of two words each, valid for the model's packed state, with
+ * exactly two ENDs.  -EINVAL, the reason in kc_last_error, for a bad program,
+ * a bad form or another property, checked before the device is touched. */
+int kc_live_create_formula(const kc_model_config *cfg, const kc_live_config *live, int form, const uint64_t *program,
+                           int n_instr, kc_live **out);
+/* Another formula for the runs that follow, on a handle of
+ * kc_live_create_formula; -EINVAL as above, and for a handle created with a
+ * built-in property.  The handle keeps the formula it had. */
+int kc_live_set_formula(kc_live *l, int form, const uint64_t *program, int n_instr);
+/* |S /\ T| and |L /\ T| of the last run of a user formula (violated iff the
+ * second is not 0); 0 and 0 for the built-in properties.  (kc_live_result keeps
+ * its layout: these two counts are read here.) */
+int kc_live_trigger_counts(kc_live *l, uint64_t *trigger_stay_out, uint64_t *trigger_live_out);
 /* The counterexample of the last run: up to `cap` states as canonical tuples
  * and the action that led to each (-1 for the Init state); returns the number
  * of states (0 if the property holds). */
@@ -1155,6 +1187,24 @@ int kc_shard_selftest(int kind, const kc_model_config *cfg, const uint64_t *par,
 int kc_live_selftest(const uint64_t *par, uint64_t npar, const uint64_t *deg, const uint64_t *edges, uint64_t ne,
                      const uint64_t *eproc, const uint64_t *stay, const uint64_t *parent, const uint64_t *level,
                      uint64_t *out, uint64_t nout, uint64_t *res, uint64_t nres);
+
+/* The two kernels of a user formula alone (csrc/live_prog.h k_live_mark_prog,
+ * csrc/live_graph.h k_live_first_trig) on made data (csrc/live_mark_selftest.hip);
+ * the data rules are kc_live_selftest's.
+ * par = [W (4, 6 or 10), form (0 / 1), n (1 .. 2^22), aft].
+ * program = n_instr instructions with exactly two ENDs, valid for W words;
+ * packed_states = n * W words; deg[n], edges[ne] = the CSR graph (targets < n,
+ * ne < 2^31); level[n] = any levels >= 1; alive_in[n] = 0 / 1, the alive bytes
+ * the first-trigger step runs on (it runs after the mark step, on trig as the
+ * mark step wrote it).
+ * out = alive, terminal, trig as the mark step wrote them: KC_EMIT_FORE + n +
+ *   aft words each.
+ * res = [stay, stay_terminal, trig_stay, first (0xffffffff = none), trig_live].
+ * Test-only. */
+int kc_live_mark_selftest(const uint64_t *par, uint64_t npar, const uint64_t *program, int n_instr,
+                          const uint64_t *packed_states, const uint64_t *deg, const uint64_t *edges, uint64_t ne,
+                          const uint64_t *level, const uint64_t *alive_in, uint64_t *out, uint64_t nout,
+                          uint64_t *res, uint64_t nres);
 
 /* ------------------------------------------------ Checkpoint streams (tests) */
 /* Device harness for the checkpoint streams (csrc/ckpt_selftest.hip) on a

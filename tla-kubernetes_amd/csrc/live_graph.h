@@ -14,6 +14,7 @@
 #include "kc_common.h"
 #include "kubeapi_spec.h"
 #include "owned.h"
+#include "pred.h"
 
 namespace kc {
 
@@ -51,6 +52,9 @@ struct LiveCounters {
   unsigned int lasso_cov;             // processes the cycle has a witness for so far
   unsigned int lasso_term, lasso_scc; // terminal[lasso_cur], comp[lasso_cur]
   unsigned int lasso_err;             // the path buffer is full
+  // a user formula (LiveArgs::trig set; 0 otherwise)
+  unsigned long long trig_stay;       // |S /\ T|
+  unsigned long long trig_live;       // |L /\ T|
 };
 
 struct LiveArgs {
@@ -79,6 +83,11 @@ struct LiveArgs {
   uint32_t* bpar;         // reach: the state that discovered this one
   uint64_t path_cap;      // entries of path
   uint32_t pmask;         // (1 << P) - 1
+  // a user formula (all null / 0 for the built-in properties)
+  uint8_t* trig;          // in the trigger set T
+  const PredInstr* prog;  // END 0 = P, END 1 = Q (pred.h), in device memory
+  int prog_n;             // its instructions
+  int form;               // 0: T = P (P ~> Q); 1: T = the Init states (<>Q)
 };
 
 // alive[] while F and L are computed: bit 0 = survived the trim, bit 1 = reaches F
@@ -143,6 +152,16 @@ __global__ void __launch_bounds__(LIVE_BLOCK) k_live_first(LiveArgs a, uint32_t 
   const uint32_t i = blockIdx.x * LIVE_BLOCK + threadIdx.x;
   const unsigned long long m = __ballot(i < n && a.alive[i]);
   if ((threadIdx.x & 63) == 0 && m) atomicMin(&a.ctr->first_alive, i + (uint32_t)(__ffsll(m) - 1));
+}
+
+// A user formula: the smallest index in L /\ T, and |L /\ T|
+__global__ void __launch_bounds__(LIVE_BLOCK) k_live_first_trig(LiveArgs a, uint32_t n) {
+  const uint32_t i = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+  const unsigned long long m = __ballot(i < n && a.alive[i] && a.trig[i]);
+  if ((threadIdx.x & 63) == 0 && m) {
+    atomicMin(&a.ctr->first_alive, i + (uint32_t)(__ffsll(m) - 1));
+    atomicAdd(&a.ctr->trig_live, (unsigned long long)__popcll(m));
+  }
 }
 
 // A single lane: the parent chain of the first L state into path[0 .. prefix),
@@ -480,6 +499,8 @@ class LiveDriver {
     return 0;
   }
 
+  uint64_t trig_stay = 0, trig_live = 0;   // a user formula's |S /\ T| and |L /\ T| after run
+
   // Everything after the mark launch (issued at t1): the trim, under
   // per-process fairness the SCCs, F and L, and the counterexample into
   // path[0 .. len).
@@ -502,6 +523,16 @@ class LiveDriver {
     res->live_terminal = h_ctr_->stay_terminal;
     res->violated = res->live_states > 0;
     if (fairness == 1) KC_TRY(fair_sccs(n, res));
+    // a user formula: L is final; violated iff a state of L is in the trigger
+    // set, and the counterexample starts at the first such state
+    if (a_.trig) {
+      hipLaunchKernelGGL(k_live_first_trig, dim3(live_grid(n)), dim3(LIVE_BLOCK), 0, st_, a_, n);
+      KC_HIP_TRY(hipGetLastError());
+      KC_TRY(read_counters());
+      trig_stay = h_ctr_->trig_stay;
+      trig_live = h_ctr_->trig_live;
+      res->violated = h_ctr_->first_alive < n;
+    }
 
     // ---- counterexample
     if (res->violated) {
@@ -509,8 +540,10 @@ class LiveDriver {
         KC_TRY(fair_lasso(n, res, len, kind, loop));
       } else {
         KC_HIP_TRY(hipMemsetAsync(a_.stamp, 0, (size_t)n * sizeof(uint32_t), st_));
-        hipLaunchKernelGGL(k_live_first, dim3(live_grid(n)), dim3(LIVE_BLOCK), 0, st_, a_, n);
-        KC_HIP_TRY(hipGetLastError());
+        if (!a_.trig) {
+          hipLaunchKernelGGL(k_live_first, dim3(live_grid(n)), dim3(LIVE_BLOCK), 0, st_, a_, n);
+          KC_HIP_TRY(hipGetLastError());
+        }
         hipLaunchKernelGGL(k_live_lasso, dim3(1), dim3(64), 0, st_, a_, n);
         KC_HIP_TRY(hipGetLastError());
         KC_TRY(read_counters());
@@ -609,8 +642,10 @@ class LiveDriver {
 
   // The counterexample under per-process fairness into path[0 .. len).
   int fair_lasso(uint32_t n, kc_live_result* res, uint32_t& len, uint32_t& kind, uint32_t& loop) {
-    hipLaunchKernelGGL(k_live_first, dim3(live_grid(n)), dim3(LIVE_BLOCK), 0, st_, a_, n);
-    KC_HIP_TRY(hipGetLastError());
+    if (!a_.trig) {
+      hipLaunchKernelGGL(k_live_first, dim3(live_grid(n)), dim3(LIVE_BLOCK), 0, st_, a_, n);
+      KC_HIP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_live_chain, dim3(1), dim3(64), 0, st_, a_, n);
     KC_HIP_TRY(hipGetLastError());
     KC_TRY(read_counters());

@@ -44,6 +44,7 @@
 #include "kc_common.h"
 #include "kubeapi_spec.h"
 #include "live_graph.h"
+#include "live_prog.h"
 #include "liveness.h"
 #include "simulate.h"
 
@@ -210,12 +211,15 @@ class LiveBase {
   virtual ~LiveBase() = default;
   virtual int setup() = 0;
   virtual int run(kc_live_result* res) = 0;
+  virtual int set_formula(int form, const PredInstr* code, int n_instr) = 0;
   virtual int trace(uint64_t* tuples, int* actions, int cap) = 0;
   virtual int alive(uint64_t* tuples, uint8_t* alive, uint64_t cap) = 0;
   virtual int64_t edge_procs(uint32_t* src, uint32_t* dst, uint8_t* proc, uint64_t cap) = 0;
   virtual int tuple_words() const = 0;
+  virtual int state_words() const = 0;
   kc_model_config cfg;
   kc_live_config live;
+  uint64_t trigger_stay = 0, trigger_live = 0;   // the last run's, 0 for the built-in properties
 };
 
 template <class M>
@@ -223,6 +227,7 @@ class LiveT : public LiveBase {
  public:
   ~LiveT() override { (void)hipSetDevice(cfg.device); }   // (the members free themselves on it)
   int tuple_words() const override { return M::TUPLE_WORDS; }
+  int state_words() const override { return M::W; }
 
   int setup() override {
     int ndev = 0;
@@ -275,6 +280,32 @@ class LiveT : public LiveBase {
     return h_ctr_.alloc(1);
   }
 
+  // A user formula (a handle of kc_live_create_formula): the program goes to
+  // the device and the trigger bytes are allocated, both on first use.
+  int set_formula(int form, const PredInstr* code, int n_instr) override {
+    if (live.property != KC_LIVE_USER) {
+      set_error("kc_live_set_formula: the handle was created with the built-in property %d "
+                "(kc_live_create_formula makes one that takes formulas)", live.property);
+      return -EINVAL;
+    }
+    static_assert(live_prog_width_ok(M::W), "k_live_mark_prog: no instantiation for this W");
+    if (const char* why = live_formula_check(form, code, n_instr, M::W)) {
+      set_error("kc_live_set_formula: %s", why);
+      return -EINVAL;
+    }
+    KC_HIP_TRY(hipSetDevice(cfg.device));
+    KC_TRY(trig_.alloc(a_.max_states));
+    KC_TRY(prog_.alloc(KC_PRED_MAX_INSTR));
+    KC_HIP_TRY(hipMemcpyAsync(prog_, code, (size_t)n_instr * sizeof(PredInstr), hipMemcpyHostToDevice, st_));
+    KC_HIP_TRY(hipStreamSynchronize(st_));   // (code is the caller's)
+    a_.trig = trig_;
+    a_.prog = prog_;
+    a_.prog_n = n_instr;
+    a_.form = form;
+    ran_ = false;
+    return 0;
+  }
+
   int run(kc_live_result* res) override {
     using clock = std::chrono::steady_clock;
     KC_HIP_TRY(hipSetDevice(cfg.device));
@@ -285,6 +316,7 @@ class LiveT : public LiveBase {
     ran_ = false;
     n_ = ne_ = 0;
     trace_.clear();
+    trigger_stay = trigger_live = 0;
 
     // ---- build
     LiveCounters zero;
@@ -343,13 +375,16 @@ class LiveT : public LiveBase {
     res->build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
 
     // ---- mark, then the trim, the SCCs and the lasso (live_graph.h)
-    hipLaunchKernelGGL((k_live_mark<M>), dim3(live_grid(n)), dim3(LIVE_BLOCK), 0, st_, a_, n);
+    if (a_.trig) live_mark_prog_launch(M::W, a_, n, st_);
+    else hipLaunchKernelGGL((k_live_mark<M>), dim3(live_grid(n)), dim3(LIVE_BLOCK), 0, st_, a_, n);
     KC_HIP_TRY(hipGetLastError());
     n_ = n;
     ne_ = ne;
     uint32_t len = 0, kind = 0, loop = 0;
     LiveDriver drv(a_, st_, h_ctr_, n, M::P);
     KC_TRY(drv.run(live.fairness == LF_Process ? 1 : 0, t1, res, len, kind, loop));
+    trigger_stay = drv.trig_stay;
+    trigger_live = drv.trig_live;
 
     // ---- counterexample
     if (res->violated) {
@@ -459,7 +494,8 @@ class LiveT : public LiveBase {
   DeviceArray<uint32_t> parent_, level_, edges_, stamp_, path_, color_, comp_, bpar_;
   DeviceArray<uint2> row_, sccw_;
   DeviceArray<LiveSlot> table_;
-  DeviceArray<uint8_t> alive_, terminal_, eproc_, enabled_, fair_;
+  DeviceArray<uint8_t> alive_, terminal_, eproc_, enabled_, fair_, trig_;
+  DeviceArray<PredInstr> prog_;   // a user formula's program (trig_ and this: only then)
   DeviceArray<LiveCounters> ctr_;
   PinnedArray<LiveCounters> h_ctr_;
   std::vector<uint64_t> trace_;   // the counterexample's packed states
@@ -485,9 +521,10 @@ struct kc_live {
   std::unique_ptr<LiveBase> impl;
 };
 
-extern "C" {
-
-int kc_live_create(const kc_model_config* cfg, const kc_live_config* live, kc_live** out) {
+// kc_live_create (code = nullptr) and kc_live_create_formula: every argument is
+// checked before the device is touched, the formula's program among them.
+static int live_create(const kc_model_config* cfg, const kc_live_config* live, int form, const PredInstr* code,
+                       int n_instr, kc_live** out) {
   if (!cfg || !live || !out) { set_error("kc_live_create: NULL argument"); return -EINVAL; }
   *out = nullptr;
   if (cfg->symmetry) {
@@ -503,9 +540,19 @@ int kc_live_create(const kc_model_config* cfg, const kc_live_config* live, kc_li
     set_error("kc_live_create: unsupported model nc=%d np=%d ns=%d", cfg->nc, cfg->np, cfg->ns);
     return -EINVAL;
   }
-  if (!live_prop_ok(cfg->nc, live->property)) {
-    set_error("kc_live_create: property %d is not defined for nc=%d (0-2 need one client; 3 any model)",
-              live->property, cfg->nc);
+  if (code) {
+    if (live->property != KC_LIVE_USER) {
+      set_error("kc_live_create_formula: property %d is not KC_LIVE_USER (a built-in property takes no formula)",
+                live->property);
+      return -EINVAL;
+    }
+    if (const char* why = live_formula_check(form, code, n_instr, impl->state_words())) {
+      set_error("kc_live_create_formula: %s", why);
+      return -EINVAL;
+    }
+  } else if (!live_prop_ok(cfg->nc, live->property)) {
+    set_error("kc_live_create: property %d is not defined for nc=%d (0-2 need one client; 3 any model; "
+              "KC_LIVE_USER comes with its formula: kc_live_create_formula)", live->property, cfg->nc);
     return -EINVAL;
   }
   impl->cfg = *cfg;
@@ -521,8 +568,21 @@ int kc_live_create(const kc_model_config* cfg, const kc_live_config* live, kc_li
     return -EINVAL;
   }
   KC_TRY(impl->setup());
+  if (code) KC_TRY(impl->set_formula(form, code, n_instr));
   *out = new kc_live{std::move(impl)};
   return 0;
+}
+
+extern "C" {
+
+int kc_live_create(const kc_model_config* cfg, const kc_live_config* live, kc_live** out) {
+  return live_create(cfg, live, 0, nullptr, 0, out);
+}
+
+int kc_live_create_formula(const kc_model_config* cfg, const kc_live_config* live, int form, const uint64_t* program,
+                           int n_instr, kc_live** out) {
+  if (!program) { set_error("kc_live_create_formula: NULL argument"); return -EINVAL; }
+  return live_create(cfg, live, form, reinterpret_cast<const PredInstr*>(program), n_instr, out);
 }
 
 void kc_live_destroy(kc_live* l) { delete l; }
@@ -530,6 +590,18 @@ void kc_live_destroy(kc_live* l) { delete l; }
 int kc_live_run(kc_live* l, kc_live_result* res) {
   if (!l || !res) { set_error("kc_live_run: NULL argument"); return -EINVAL; }
   return l->impl->run(res);
+}
+
+int kc_live_set_formula(kc_live* l, int form, const uint64_t* program, int n_instr) {
+  if (!l || !program) { set_error("kc_live_set_formula: NULL argument"); return -EINVAL; }
+  return l->impl->set_formula(form, reinterpret_cast<const PredInstr*>(program), n_instr);
+}
+
+int kc_live_trigger_counts(kc_live* l, uint64_t* trigger_stay_out, uint64_t* trigger_live_out) {
+  if (!l || !trigger_stay_out || !trigger_live_out) { set_error("kc_live_trigger_counts: NULL argument"); return -EINVAL; }
+  *trigger_stay_out = l->impl->trigger_stay;
+  *trigger_live_out = l->impl->trigger_live;
+  return 0;
 }
 
 int kc_live_trace(kc_live* l, uint64_t* tuples_out, int* actions_out, int cap) {

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from ._lib import (ACTION_CONSTRAINTS, ACTION_PROPERTIES, ACTIONS, CKPT_SECTIONS, CUTS, ERR_KINDS, FAIRNESS, INSTANTIATIONS, INVARIANTS,
-                   LIVE_KINDS, PROPERTIES, SIM_KINDS,
+                   LIVE_FORMS, LIVE_KINDS, LIVE_USER, PROPERTIES, SIM_KINDS,
                    KcCheckpointInfo, KcCheckpointOptions, KcLiveConfig,
                    KcLiveResult, KcModelConfig, KcResult, KcSimConfig,
                    KcSimResult, KcSqueueConfig, KcSqueueStats, KubecheckError,
@@ -625,6 +625,9 @@ class LiveResult:
     fair_states: int = 0              # |F|
     scc_rounds: int = 0               # launches of the SCC and closure phases that end in a counter read
     scc_ms: float = 0.0
+    formula: Optional[str] = None     # a user formula's text; the fields below are 0 for a built-in property
+    trigger_stay: int = 0             # |S /\ T|: stay states in the trigger set
+    trigger_live: int = 0             # |L /\ T|: violated iff not 0
 
 
 class LivenessChecker:
@@ -633,14 +636,34 @@ class LivenessChecker:
     behaviour can stay in, and a lasso counterexample.  `property` is a name of
     PROPERTIES or its index; `fairness` a name of FAIRNESS: "next" is
     WF_vars(Next), "process" weak fairness of every process (PlusCal's `fair
-    process`), decided on the fair SCCs of the stay states."""
+    process`), decided on the fair SCCs of the stay states.
 
-    def __init__(self, cfg: Optional[ModelConfig] = None, property="ReconcileCompletes",
-                 max_states: Optional[int] = None, fairness: str = "next", **kw):
+    `formula` instead of `property` checks a temporal formula of the user's:
+    P ~> Q, [](P => <>Q), []<>Q or <>Q over predicates of kubecheck.pred
+    (pred.parse_temporal), reported under `name`; set_formula()
+    gives such a handle another one.  `program=(form, program)` does the same
+    with a compiled pair of predicates (pred.compile_temporal).  property=-1
+    alone is refused by the library: a handle never lacks its formula."""
+
+    def __init__(self, cfg: Optional[ModelConfig] = None, property=None,
+                 max_states: Optional[int] = None, fairness: str = "next", *, formula: Optional[str] = None,
+                 name: Optional[str] = None, program=None, **kw):
         if fairness not in FAIRNESS:
             raise ValueError(f"unknown fairness {fairness!r}; known: {FAIRNESS}")
         self.fairness = fairness
         self.cfg = cfg or ModelConfig(**kw)
+        if (formula is not None) + (property is not None) + (program is not None) > 1:
+            raise ValueError("LivenessChecker: give `property` (a built-in) or `formula` (or `program`), not both")
+        self.formula = formula
+        self.name = name
+        compiled = program
+        if formula is not None:
+            # compiled before anything is allocated: a bad formula is a pred.PredError
+            compiled = pred.compile_temporal(formula, self.cfg.nc, self.cfg.np, self.cfg.ns)
+        if compiled is not None:
+            property = LIVE_USER
+        elif property is None:
+            property = "ReconcileCompletes"
         if isinstance(property, str):
             if property not in PROPERTIES:
                 raise ValueError(f"unknown property {property!r}; known: {PROPERTIES}")
@@ -650,21 +673,50 @@ class LivenessChecker:
         self._h = C.c_void_p()
         self._c = self.cfg.to_c()
         self._l = KcLiveConfig(self.property, int(max_states or 0), FAIRNESS.index(fairness))
-        check("kc_live_create", self._lib.kc_live_create(C.byref(self._c), C.byref(self._l), C.byref(self._h)))
+        if compiled is not None:
+            form, arr, n_instr = self._program_args(*compiled)
+            check("kc_live_create_formula", self._lib.kc_live_create_formula(
+                C.byref(self._c), C.byref(self._l), form, arr, n_instr, C.byref(self._h)))
+        else:
+            check("kc_live_create", self._lib.kc_live_create(C.byref(self._c), C.byref(self._l), C.byref(self._h)))
         self.tuple_words = self._lib.kc_spec_tuple_words(self.cfg.nc, self.cfg.np, self.cfg.ns)
+
+    @staticmethod
+    def _program_args(form, program):
+        if isinstance(form, str):
+            form = LIVE_FORMS.index(form)
+        words = list(program.words if hasattr(program, "words") else program)
+        return int(form), (C.c_uint64 * max(1, len(words)))(*words), len(words) // 2
+
+    def set_formula(self, formula: str, name: Optional[str] = None) -> None:
+        """The formula the runs that follow check (a handle made with `formula` or `program`)."""
+        self.set_program(*pred.compile_temporal(formula, self.cfg.nc, self.cfg.np, self.cfg.ns))
+        self.formula, self.name = formula, name if name is not None else self.name
+
+    def set_program(self, form, program) -> None:
+        """kc_live_set_formula with a compiled program (a pred.Program or its
+        words): form 0 / "leads-to" or 1 / "eventually"; exactly two predicates,
+        END 0 = P and END 1 = Q.  KubecheckError -22 where the library refuses."""
+        form, arr, n_instr = self._program_args(form, program)
+        check("kc_live_set_formula", self._lib.kc_live_set_formula(self._h, form, arr, n_instr))
 
     def run(self) -> LiveResult:
         r = KcLiveResult()
         check("kc_live_run", self._lib.kc_live_run(self._h, C.byref(r)))
+        ts, tl = C.c_uint64(), C.c_uint64()
+        check("kc_live_trigger_counts", self._lib.kc_live_trigger_counts(self._h, C.byref(ts), C.byref(tl)))
+        user = self.property == LIVE_USER
         res = LiveResult(
-            property=PROPERTIES[self.property], states=r.states, edges=r.edges, init=r.init, depth=r.depth,
+            property=(self.name or "formula") if user else PROPERTIES[self.property],
+            states=r.states, edges=r.edges, init=r.init, depth=r.depth,
             stay_states=r.stay_states, live_states=r.live_states, live_terminal=r.live_terminal,
             rounds=r.rounds, error=ERR_KINDS.get(r.err_kind),
             error_action=ACTIONS[r.err_action] if 0 <= r.err_action < len(ACTIONS) else None,
             error_self=r.err_self, violated=bool(r.violated), kind=LIVE_KINDS.get(r.kind),
             prefix_len=r.prefix_len, trace_len=r.trace_len, loop_start=r.loop_start, seconds=r.seconds,
             build_ms=r.build_ms, trim_ms=r.trim_ms, fairness=self.fairness, sccs=r.sccs, fair_sccs=r.fair_sccs,
-            fair_states=r.fair_states, scc_rounds=r.scc_rounds, scc_ms=r.scc_ms)
+            fair_states=r.fair_states, scc_rounds=r.scc_rounds, scc_ms=r.scc_ms,
+            formula=self.formula if user else None, trigger_stay=ts.value, trigger_live=tl.value)
         if res.violated:
             n = res.trace_len
             out = np.zeros((n, self.tuple_words), dtype=np.uint64)

@@ -125,6 +125,9 @@ class KcSimResult(C.Structure):
 
 # temporal properties kc_live_* checks (kc_live_config.property = the index)
 PROPERTIES = ("ReconcileCompletes", "CleansUpProperly", "ClientRestarts", "SomeActorRestarts")
+# kc_live_config.property of a user formula (kc_live_create_formula); the forms it takes
+LIVE_USER = -1
+LIVE_FORMS = ("leads-to", "eventually")
 # how a liveness counterexample ends (kc_live_result.kind)
 LIVE_KINDS = {0: None, 1: "back-to-state", 2: "stuttering"}
 
@@ -296,6 +299,12 @@ SIGNATURES = [
     ("kc_live_create", C.c_int, [C.POINTER(KcModelConfig), C.POINTER(KcLiveConfig), C.POINTER(_P)]),
     ("kc_live_destroy", None, [_P]),
     ("kc_live_run", C.c_int, [_P, C.POINTER(KcLiveResult)]),
+    ("kc_live_create_formula", C.c_int, [C.POINTER(KcModelConfig), C.POINTER(KcLiveConfig), C.c_int, _U64P, C.c_int,
+                                         C.POINTER(_P)]),
+    ("kc_live_set_formula", C.c_int, [_P, C.c_int, _U64P, C.c_int]),
+    ("kc_live_trigger_counts", C.c_int, [_P, _U64P, _U64P]),
+    ("kc_live_mark_selftest", C.c_int, [_U64P, C.c_uint64, _U64P, C.c_int, _U64P, _U64P, _U64P, C.c_uint64, _U64P, _U64P,
+                                        _U64P, C.c_uint64, _U64P, C.c_uint64]),
     ("kc_live_trace", C.c_int, [_P, _U64P, _IP, C.c_int]),
     ("kc_live_trace_text", C.c_int64, [_P, C.c_char_p, C.c_size_t]),
     ("kc_live_alive", C.c_int, [_P, _U64P, _U8P, C.c_uint64]),

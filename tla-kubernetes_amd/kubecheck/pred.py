@@ -11,6 +11,11 @@ Three parts, which share the AST and nothing else:
 * :func:`compile_invariants` lowers ASTs to 16-byte instructions over the
   packed state's words.
 
+Temporal formulas are two such predicates and a shape:
+:func:`parse_temporal` splits P ~> Q, [](P => <>Q), []<>Q and <>Q into (form,
+P, Q) and refuses every other shape by name; :func:`compile_temporal` compiles
+the pair into one program (END 0 = P, END 1 = Q) for kubecheck.LivenessChecker.
+
 Language
   atoms        pc[a]  op[a]  kind[a]  shouldReconcile[a] (clients)  Len(stack[a])
                a \\in DOMAIN requests      requests[a].op      requests[a].status
@@ -491,6 +496,168 @@ def parse_definitions(text: str) -> Dict[str, str]:
     return defs
 
 
+# ---------------------------------------------------------- temporal formulas
+# A formula is two state predicates and one of three shapes:
+#   P ~> Q, [](P => <>Q)   form 0, trigger P
+#   []<>Q                  form 0, trigger TRUE
+#   <>Q                    form 1, trigger = the Init states
+# The split works on the text, outside (), [], {} and strings; the operands go
+# to parse().  `[]` next to pc["Client"] is no problem: the box is `[` directly
+# followed by `]`, which the predicate language never writes.
+_SHAPES = "P ~> Q, [](P => <>Q), []<>Q or <>Q over state predicates P, Q"
+
+
+def _scan_temporal(text: str) -> List[Tuple[int, str, int]]:
+    """(position, operator, nesting depth) of every ~>, <> and [] outside strings."""
+    out, depth, i = [], 0, 0
+    while i < len(text):
+        c = text[i]
+        if c == '"':
+            j = text.find('"', i + 1)
+            if j < 0:
+                raise PredError("a string without its closing quote")
+            i = j + 1
+            continue
+        if text[i:i + 2] in ("~>", "<>", "[]"):
+            out.append((i, text[i:i + 2], depth))
+            i += 2
+            continue
+        if c in "([{":
+            depth += 1
+        elif c in ")]}":
+            depth -= 1
+            if depth < 0:
+                raise PredError(f"unbalanced {c!r}")
+        i += 1
+    if depth:
+        raise PredError("unbalanced brackets")
+    return out
+
+
+def _top_level(text: str, what: Sequence[str]) -> int:
+    """The position of the first of `what` at nesting depth 0 outside strings, or -1."""
+    depth, i = 0, 0
+    while i < len(text):
+        c = text[i]
+        if c == '"':
+            i = text.find('"', i + 1) + 1 or len(text)
+            continue
+        if depth == 0 and any(text.startswith(w, i) for w in what):
+            return i
+        if c in "([{":
+            depth += 1
+        elif c in ")]}":
+            depth -= 1
+        i += 1
+    return -1
+
+
+def _strip_parens(text: str) -> str:
+    """text without the parentheses that enclose all of it."""
+    text = text.strip()
+    while text.startswith("("):
+        depth, i, close = 0, 0, -1
+        while i < len(text):
+            c = text[i]
+            if c == '"':
+                i = text.find('"', i + 1) + 1 or len(text)
+                continue
+            if c in "([{":
+                depth += 1
+            elif c in ")]}":
+                depth -= 1
+                if depth == 0:
+                    close = i
+                    break
+            i += 1
+        if close != len(text) - 1:
+            break
+        text = text[1:-1].strip()
+    return text
+
+
+def _temporal_operand(text: str, of: str, prefix: bool) -> str:
+    """An operand of the temporal operator `of`: it holds no temporal operator,
+    and where TLA+'s precedences would read it differently from the way it is
+    split here (a prefix operator binds tighter than every connective, ~> looser
+    than /\\ and \\/ but tighter than =>) it must be parenthesised."""
+    s = text.strip()
+    if not s:
+        raise PredError(f"{of} lacks an operand")
+    inner = _scan_temporal(s)
+    if inner:
+        _, op, depth = inner[0]
+        if depth == 0:
+            raise PredError(f"more than one temporal operator ({op} in an operand of {of}): a formula is {_SHAPES}")
+        raise PredError(f"the temporal operator {op} inside an operand of {of}: nested temporal formulas are not "
+                        f"supported; a formula is {_SHAPES}")
+    connectives = ("/\\", "\\/", "=>", "<=>", "\\land", "\\lor") if prefix else ("=>", "<=>")
+    if _strip_parens(s) == s and _top_level(s, connectives) >= 0:
+        raise PredError(f"parenthesise the operand of {of}: {s[:30]!r} has a connective that binds "
+                        f"{'looser' if prefix else 'no tighter'} than {of}")
+    return s
+
+
+def parse_temporal(text: str, nc: int = 1, np: int = 1, ns: int = 1):
+    """(form, P_ast, Q_ast) of a temporal formula for the model (nc, np, ns):
+    form 0 for P ~> Q, [](P => <>Q) and []<>Q (P = TRUE), form 1 for <>Q (P =
+    TRUE; the trigger is the Init states).  Raises PredError, naming what it
+    saw, for <>[]Q, a bare []P, more than one temporal operator, a temporal
+    operator inside an operand and a text with no temporal operator."""
+    body = _strip_parens(re.sub(r"\\\*[^\n]*", " ", text))
+    if not body:
+        raise PredError("empty formula")
+    ops = _scan_temporal(body)
+    if not ops:
+        raise PredError(f"no temporal operator in {body[:30]!r}: a state predicate: list it under INVARIANT")
+    true = ("const", True)
+
+    def sub(s):
+        return parse(s, nc, np, ns)
+
+    if body.startswith("[]"):
+        rest = body[2:].lstrip()
+        if rest.startswith("<>"):
+            return 0, true, sub(_temporal_operand(rest[2:], "[]<>", True))
+        inner = _strip_parens(rest)
+        if not _scan_temporal(inner):
+            _temporal_operand(rest, "[]", True)
+            raise PredError(f"[]P with a state predicate P ({inner[:30]!r}) is an invariant: list P under INVARIANT")
+        if inner == rest.strip():
+            raise PredError(f"[] over an unparenthesised temporal formula ({rest[:30]!r}): combined temporal "
+                            f"formulas are not supported; a formula is {_SHAPES}")
+        at = _top_level(inner, ("=>", "<=>"))
+        rhs = inner[at + 2:].lstrip() if at >= 0 and not inner.startswith("<=>", at) else ""
+        if at >= 0 and rhs.startswith("<>") and not (at and inner[at - 1] == "<"):
+            if rhs[2:].lstrip().startswith("[]"):
+                raise PredError(f"<>[]Q under [] ({rhs[:30]!r}): nested temporal formulas are not supported")
+            return 0, sub(_temporal_operand(inner[:at], "[](P => <>Q)", False)), \
+                sub(_temporal_operand(rhs[2:], "[](P => <>Q)", True))
+        raise PredError(f"[] over {inner[:30]!r}: neither P => <>Q nor a state predicate; nested or combined "
+                        f"temporal formulas are not supported; a formula is {_SHAPES}")
+    if body.startswith("<>"):
+        rest = body[2:].lstrip()
+        if rest.startswith("[]"):
+            raise PredError("<>[]Q (eventually always) is not a stay-set question: it needs an acceptance condition "
+                            f"on the SCCs of the whole graph; a formula is {_SHAPES}")
+        return 1, true, sub(_temporal_operand(rest, "<>", True))
+    top = [o for o in ops if o[1] == "~>" and o[2] == 0]
+    if len(top) > 1:
+        raise PredError(f"more than one temporal operator (~> twice): a formula is {_SHAPES}")
+    if not top:
+        _, op, depth = ops[0]
+        where = "inside an operand" if depth else "combined with a connective"
+        raise PredError(f"the temporal operator {op} {where} in {body[:30]!r}: nested or combined temporal formulas "
+                        f"are not supported; a formula is {_SHAPES}")
+    at = top[0][0]
+    return 0, sub(_temporal_operand(body[:at], "~>", False)), sub(_temporal_operand(body[at + 2:], "~>", False))
+
+
+def has_temporal(text: str) -> bool:
+    """Does the text hold a temporal operator (~>, <>, []) outside strings?"""
+    return bool(_scan_temporal(re.sub(r"\\\*[^\n]*", " ", text)))
+
+
 # ----------------------------------------------------------- direct evaluation
 _TUPLE_PER_PROC = 19
 _TUPLE_FIELD = {"pc": 0, "op": 1, "kind": 3, "sr": 4, "stacklen": 5, "rq_present": 11, "rq_op": 12,
@@ -750,3 +917,10 @@ def compile_invariants(invariants, nc: int = 1, np: int = 1, ns: int = 1) -> Pro
             raise PredError(f"{name}: the program reaches {len(em.code)} instructions: at most {MAX_INSTR} over all "
                             "the invariants of a run")
     return Program(list(invariants), em.code, em.max_depth, lay)
+
+
+def compile_temporal(text: str, nc: int = 1, np: int = 1, ns: int = 1) -> Tuple[int, Program]:
+    """(form, program) of a temporal formula (parse_temporal): the program always holds exactly two predicates,
+    END 0 = the trigger P ("trigger"; TRUE for []<>Q and <>Q) and END 1 = the goal Q ("goal")."""
+    form, p_ast, q_ast = parse_temporal(text, nc, np, ns)
+    return form, compile_invariants({"trigger": p_ast, "goal": q_ast}, nc, np, ns)

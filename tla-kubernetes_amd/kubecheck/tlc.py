@@ -112,6 +112,18 @@ unknown-invariant error it always was.  A user invariant with -simulate, a
 PROPERTY list, SYMMETRY, CONSTRAINT / ACTION_CONSTRAINT, -coverage or the
 checkpoint flags is an error (models/Reach.cfg, models/Reach.tla).
 
+User-defined temporal properties: a PROPERTY name that is neither one of
+kubecheck.PROPERTIES nor an action property and that the `-defs` file defines
+is a temporal formula of the user's: P ~> Q, [](P => <>Q), []<>Q or <>Q over
+kubecheck.pred's predicates (pred.parse_temporal).  It is
+checked in cfg order with the built-in ones, by the same LivenessChecker under
+the same fairness, with the same 2192 / 2116 / 2264 / 2217 messages and exit
+code 13 (models/Eventually.cfg, models/Eventually.tla).  A definition without a
+temporal operator listed under PROPERTY, <>[]Q, a bare []P and nested or
+combined temporal formulas are errors that name the shape.  What a PROPERTY
+list is refused with (-simulate, SYMMETRY, CONSTRAINT, -coverage, the
+checkpoint flags, user INVARIANTs) is refused with these too.
+
 `-fairness process` checks the properties under weak
 fairness of every process (PlusCal's `fair process`; a .cfg cannot say this,
 so it is an option) instead of WF_vars(Next), the default; the 2192 line names
@@ -304,11 +316,38 @@ def split_user_invariants(cfg: dict, defs: Optional[Dict[str, str]], procs=(1, 1
     return dict(cfg, invariants=[x for x in cfg["invariants"] if x not in user]), user
 
 
-def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, checkpointing: bool = False):
+def split_user_properties(cfg: dict, defs: Optional[Dict[str, str]], procs=(1, 1, 1)) -> Dict[str, str]:
+    """The PROPERTY names of a parsed cfg that are neither kubecheck's
+    PROPERTIES nor action properties and that `defs` (-defs FILE: name ->
+    text) defines: {name: formula text} in cfg order.  Each is compiled here
+    (no GPU), so a definition without a temporal operator, a shape that is not
+    supported or a bad predicate is a CfgError before anything runs.  A name
+    defined nowhere stays the unknown-property error it always was."""
+    from . import pred
+    from ._lib import PROPERTIES
+
+    user: Dict[str, str] = {}
+    for x in cfg["properties"]:
+        if x in PROPERTIES or x in ACTION_PROPERTY_NAMES or not defs or x not in defs or x in user:
+            continue
+        try:
+            if not pred.has_temporal(defs[x]):
+                raise CfgError(f"PROPERTY {x}: its definition has no temporal operator (~>, <>, []): a state "
+                               "predicate: list it under INVARIANT")
+            pred.compile_temporal(defs[x], *procs)
+        except pred.PredError as e:
+            raise CfgError(f"user-defined PROPERTY {x}: {e}") from None
+        user[x] = defs[x]
+    return user
+
+
+def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, checkpointing: bool = False,
+                   user_props: Optional[Dict[str, str]] = None):
     """model_from_cfg for a cfg that may list temporal properties: (ModelConfig
     kwargs, the PROPERTY names in cfg order).  The names must be kubecheck's
-    PROPERTIES; simulation mode checks none.  coverage: -coverage was given;
-    checkpointing: one of -checkpoint, -checkpointlevels, -recover was."""
+    PROPERTIES or keys of user_props (split_user_properties: the user's
+    temporal formulas); simulation mode checks none.  coverage: -coverage was
+    given; checkpointing: one of -checkpoint, -checkpointlevels, -recover was."""
     from ._lib import PROPERTIES
 
     # a PROPERTY list may mix temporal names (the liveness phase, after a clean
@@ -355,10 +394,11 @@ def check_from_cfg(cfg: dict, simulate: bool = False, coverage: bool = False, ch
     if coverage and cfg.get("symmetry"):
         raise CfgError(f"-coverage with SYMMETRY {cfg['symmetry']}: the states explored stand for orbits, "
                        "so the counts would be no evaluation counts")
-    bad = [x for x in props if x not in PROPERTIES]
+    bad = [x for x in props if x not in PROPERTIES and x not in (user_props or {})]
     if bad:
         raise CfgError(f"unknown temporal property(ies) {bad}; known: {PROPERTIES}; "
-                       f"action properties: {ACTION_PROPERTY_NAMES}")
+                       f"action properties: {ACTION_PROPERTY_NAMES}; a formula of your own: define it in the "
+                       "-defs file")
     if props and simulate:
         raise CfgError("-simulate checks no temporal PROPERTY (liveness needs the whole state graph)")
     if cfg.get("symmetry") and props:
@@ -1096,6 +1136,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     defs = parse_defs(open(tla_path).read()) if os.path.exists(tla_path) else {}
     parsed = parse_cfg(open(cfg_path).read(), defs)
     user_inv = {}
+    user_props: Dict[str, str] = {}
     if a.defs:
         from . import pred
         if not os.path.exists(a.defs):
@@ -1107,8 +1148,9 @@ def main(argv: Optional[List[str]] = None) -> int:
             raise CfgError(f"-defs {a.defs}: {e}") from None
         parsed, user_inv = split_user_invariants(parsed, user_defs, (a.nc, a.np, a.ns), a.simulate, a.coverage,
                                                  a.checkpointing)
+        user_props = split_user_properties(parsed, user_defs, (a.nc, a.np, a.ns))
     try:
-        kw, props = check_from_cfg(parsed, a.simulate, a.coverage, a.checkpointing)
+        kw, props = check_from_cfg(parsed, a.simulate, a.coverage, a.checkpointing, user_props)
     except CfgError as e:
         # (a refused combination with the checkpoint flags or with a cfg's
         # constraints ends in an Error line; the older refusals raise, as they did)
@@ -1173,8 +1215,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     for name in props:
         print(msg(2192, live_start_message(name, a.fairness, r.distinct, time.time()), 0, a.tool), flush=True)
         # (the liveness phase has no part in the action properties: the BFS checked them)
-        with kubecheck.LivenessChecker(dataclasses.replace(mc_cfg, action_properties=0), name,
-                                       fairness=a.fairness) as lc:
+        which = dict(formula=user_props[name], name=name) if name in user_props else dict(property=name)
+        with kubecheck.LivenessChecker(dataclasses.replace(mc_cfg, action_properties=0), fairness=a.fairness,
+                                       **which) as lc:
             lr = lc.run()
         t1 += lr.seconds
         if lr.error is not None or (lr.states, lr.edges) != (r.distinct, r.generated - r.init):

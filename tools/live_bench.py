@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timings of the liveness check (kubecheck.LivenessChecker) on one GPU.
 
-    python tools/live_bench.py [--reps 3] [--fairness next|process] [--json OUT.json] [--md OUT.md]
+    python tools/live_bench.py [--reps 3] [--fairness next|process] [--formulas] [--json OUT.json] [--md OUT.md]
 
 For Model_1 and for NP=2 with both constants FALSE, every property: the size of
 the graph, |S| and |L|, the trim rounds, and build_ms (the graph build), trim_ms
@@ -10,7 +10,10 @@ after one warm-up run on the same handle.  Writes one JSON document and the
 table of DESIGN.md §7.12.  With --fairness process (per-process weak fairness,
 the fair SCCs) the rows also hold the SCC counts, |F|, the SCC phase's launches
 and scc_ms, the JSON goes to profiles/live_bench_fair.json unless --json says
-otherwise, and the table is the one of DESIGN.md §7.13.
+otherwise, and the table is the one of DESIGN.md §7.13.  With --formulas every
+model gets further rows: the built-in properties spelled as user formulas
+(DESIGN.md §4.14, §7.22), which take the program-driven mark kernel and the
+first-trigger launch in place of the compiled stay predicate.
 """
 from __future__ import annotations
 
@@ -23,6 +26,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tla-kubernetes_amd"))
 
 MODELS = [("Model_1", dict()), ("NP=2, constants FALSE", dict(np=2, can_fail=False, can_timeout=False))]
+# the built-in properties as a user writes them (row name -> formula)
+FORMULAS = {
+    "ReconcileCompletes as a formula": 'shouldReconcile["Client"] ~> ~shouldReconcile["Client"]',
+    "ClientRestarts as a formula": '[]<>(pc["Client"] = "CStart")',
+    "SomeActorRestarts as a formula":
+        r'[]<>((\E c \in Clients : pc[c] = "CStart") \/ (\E p \in Controllers : pc[p] = "PVCStart"))',
+}
 
 
 def main() -> int:
@@ -31,6 +41,7 @@ def main() -> int:
     ap.add_argument("--json", default=None)
     ap.add_argument("--md", default=None)
     ap.add_argument("--fairness", choices=("next", "process"), default="next")
+    ap.add_argument("--formulas", action="store_true", help="also the built-ins spelled as user formulas")
     a = ap.parse_args()
     fair = a.fairness == "process"
     if fair and a.json is None:
@@ -44,8 +55,11 @@ def main() -> int:
     doc = {"what": "liveness check timings", "reps": a.reps, "fairness": a.fairness,
            "build": kubecheck.load().kc_build_info().decode(), "runs": []}
     for name, flags in MODELS:
-        for prop in kubecheck.PROPERTIES:
-            with kubecheck.LivenessChecker(kubecheck.ModelConfig(**flags), prop, fairness=a.fairness) as lc:
+        rows = [(p, dict(property=p)) for p in kubecheck.PROPERTIES]
+        if a.formulas:
+            rows += [(n, dict(formula=f, name=n)) for n, f in FORMULAS.items()]
+        for prop, which in rows:
+            with kubecheck.LivenessChecker(kubecheck.ModelConfig(**flags), fairness=a.fairness, **which) as lc:
                 lc.run()                                    # warm-up
                 runs = [lc.run() for _ in range(a.reps)]
             r = runs[0]
